@@ -11,10 +11,18 @@ candidates and runs 20 L-BFGS-B restarts (q=1) on the analytic device gradient. 
 = (raw samples + optimiser evaluations x batch) / ask wall time — SURVEY.md §8(d)'s
 definition of ask() candidates/s — over K timed asks after W warm-up asks.
 
-Also reported: ``eval_pass`` (one forward + backward over b=512 candidates resident in HBM
-through the native plan, the unit raw screening is made of, with its per-kernel rooflines
-and PMC traffic), the per-kernel table at the restart batch (the top-level ``roofline`` is
-its dominant op), the GP posterior of the ask's fitted model, and the CPU baseline (the
+A plain run does only that: tell() once cold and once warm, W warm-up asks, K timed asks,
+the result line.  ``--dump-outputs DIR`` also writes what the last timed ask returned to its
+caller as ``DIR/<name>.npy`` (float64): ``candidate`` (the candidate frame's columns, named
+in the line's ``outputs``) and ``acq_value`` (the acquisition value optimize_acqf returned
+for it).  Problem, seeds, warm-up and step counts fix every input, so two builds run with
+the same arguments can be compared output for output.
+
+With ``--full`` also reported: ``eval_pass`` (one forward + backward over b=512 candidates
+resident in HBM through the native plan, the unit raw screening is made of, with its
+per-kernel rooflines and PMC traffic), the per-kernel table at the restart batch (the
+top-level ``roofline`` is its dominant op), qLogNEHVI, the Cholesky figures, the GP posterior
+of the ask's fitted model, the config-1 Detergent loop, and the CPU baseline (the
 reference-structure oracle on the host cores, composed from bounded samples of each ask
 phase).
 
@@ -23,10 +31,11 @@ torchrun with WORLD_SIZE = N).  One ask is a sequential, latency-bound optimisat
 20 restarts are ONE joint L-BFGS-B problem (batch_limit = num_restarts, BoFire's default)
 whose every iteration waits on the previous evaluation — so N GPUs serve N asks: ``value``
 at N > 1 is replicas (weak scaling), every rank running the complete N = 1 workload with
-its own seed and no collective in the timed region.  ``sharded_ask`` then times the single
-ask sharded over the ranks (config 4's layout): raw screening in N shards
-with an all-gather of the values, the joint restart problem replicated on every rank with
-each rank evaluating its slice per iteration and all-gathering (value, gradient).
+its own seed and no collective in the timed region.  With ``--full``, ``sharded_ask`` then
+times the single ask sharded over the ranks (config 4's layout): raw
+screening in N shards with an all-gather of the values, the joint restart problem replicated
+on every rank with each rank evaluating its slice per iteration and all-gathering (value,
+gradient).
 
 Prints ONE JSON line on rank 0.
 """
@@ -430,7 +439,7 @@ def cpu_full_ask(s, restarts, raw, S, seed=0):
     over 2048 posterior draws, S per-sample Python box decompositions, ``raw`` raw samples in
     chunks of batch_limit, then scipy L-BFGS-B over the joint ``restarts`` problem with the
     autograd gradient, on the GPU ask's fitted GPs.  Returns a dict of phase times and
-    evaluation counts (minutes of CPU work: run with --cpu-full-ask, not by default)."""
+    evaluation counts (minutes of CPU work: run with --full --cpu-full-ask, not by default)."""
     from everest_amd.optim import optimize_acqf
     from oracle import gp as ogp
     from oracle import qnehvi as oq
@@ -556,6 +565,22 @@ def _ask_evals(s) -> int:
     return int(st.raw_evals + getattr(st, "opt_evals_global", st.opt_evals))
 
 
+def dump_outputs(path: str, cand, stats, rank: int) -> dict:
+    """Write what the last timed ask() returned to its caller as float64 ``.npy`` files under
+    ``path`` (a few hundred bytes): the candidate frame (inputs, predictions, standard
+    deviations, desirabilities; one row per candidate) and the acquisition value
+    optimize_acqf returned for it.  Ranks > 0 of a replica run add ``_rank<r>`` to the names.
+    Returns the line's ``outputs`` entry."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    arrays = {f"candidate{sfx}": np.ascontiguousarray(cand.to_numpy(dtype=np.float64)),
+              f"acq_value{sfx}": np.atleast_1d(np.asarray(stats.best_value, dtype=np.float64))}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"files": {name + ".npy": list(a.shape) for name, a in arrays.items()},
+            "candidate_columns": [str(c) for c in cand.columns]}
+
+
 def _spawn_ranks(n: int) -> int:
     """``bench.py --gpus N`` without a launcher: start N fresh ranks (one process per GPU,
     torchrun-style env, RCCL rendezvous on 127.0.0.1) from a parent that never touches HIP,
@@ -638,6 +663,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10, help="timed ask() calls")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed ask() returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed asks also measure everything else the line can hold: per-kernel and "
+                         "roofline figures, the evaluation pass, qLogNEHVI, Cholesky, GP posterior, the config-1 "
+                         "loop, the CPU baseline, and at --gpus N > 1 the sharded ask (minutes)")
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--d", type=int, default=6)
     ap.add_argument("--m", type=int, default=5)
@@ -646,14 +677,21 @@ def main():
     ap.add_argument("--restarts", type=int, default=20)
     ap.add_argument("--b", type=int, default=512, help="candidates per rank of the evaluation pass")
     ap.add_argument("--eval-steps", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-full-ask", default=None, metavar="JSON",
-                    help="also run one FULL reference-structure ask on the host (minutes) and write it to JSON")
-    ap.add_argument("--no-eval-pass", action="store_true", help="skip the b-candidate evaluation-pass figures")
-    ap.add_argument("--no-config1", action="store_true", help="skip the configs[0] Detergent ask/tell loop timing")
+                    help="with --full: also run one FULL reference-structure ask on the host (minutes) and write "
+                         "it to JSON")
+    ap.add_argument("--no-eval-pass", action="store_true",
+                    help="with --full: skip the b-candidate evaluation-pass figures")
+    ap.add_argument("--no-config1", action="store_true",
+                    help="with --full: skip the configs[0] Detergent ask/tell loop timing")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "hbm_traffic.json"),
-                    help="per-launch HBM bytes from a rocprofv3 --pmc pass (tools/pmc_traffic.py)")
+                    help="with --full: per-launch HBM bytes from a rocprofv3 --pmc pass (tools/pmc_traffic.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.cpu_full_ask and not args.full:
+        ap.error("--cpu-full-ask is a leg of --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(_spawn_ranks(args.gpus))            # parent: no HIP call before the ranks start
@@ -706,7 +744,7 @@ def main():
     t0 = time.perf_counter()
     evals = 0
     for _ in range(args.steps):
-        s.ask(1)
+        cand = s.ask(1)
         evals += _ask_evals(s)
     sync()
     dt = maxed(time.perf_counter() - t0)
@@ -716,6 +754,48 @@ def main():
         evals = int(et.item())
     value = evals / dt
     ms = dt / args.steps * 1e3
+    outputs = dump_outputs(args.dump_outputs, cand, s.last_ask_stats, rank) if args.dump_outputs else None
+    # the fields every run prints; --full appends its legs below
+    line = {
+        "metric": "QnehviStrategy.ask() candidates/sec + GP posterior ms, n=512 d=6 m=5",
+        "value": round(value, 1),
+        "unit": "candidates/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (DTLZ2 d=6 m=5 train set; GPs fitted on device by tell())",
+        "config": {"workload": "full QnehviStrategy.ask() of BASELINE configs[3] (config 4): DTLZ2(d=6,m=5), "
+                               f"n_train={args.n}, S={args.S} MC samples, {args.raw} raw Sobol candidates + "
+                               f"{args.restarts} L-BFGS-B restarts, q=1; value = (raw + optimiser "
+                               "evaluations x batch) / ask wall time, SURVEY.md §8(d)",
+                   "n_train": args.n, "d": args.d, "m": args.m, "mc_samples": args.S, "raw_samples": args.raw,
+                   "restarts": args.restarts, "batch_limit": args.restarts,
+                   "parallelism": (f"replicas: {world} ranks, one full ask each (seeds 1..{world}), no "
+                                   "collective in the timed region; the single ask sharded over the ranks in "
+                                   "sharded_ask (--full)" if world > 1 else "1 rank")},
+    }
+    acqf_ask = s.last_acqf
+    st_ask = s.last_ask_stats
+    tm = getattr(acqf_ask, "timings", {})
+    phases = {"construction_s": round(tm.get("total", 0.0), 4), "construction": {k: round(v, 4) for k, v in tm.items()},
+              "raw_screening_s": round(st_ask.t_raw, 4), "restarts_s": round(st_ask.t_opt, 4),
+              "optimizer_iterations": st_ask.opt_iters, "evals_last_ask": _ask_evals(s),
+              "driver": st_ask.chunks[0]["driver"] if st_ask.chunks else None}
+    ask = {"ask_s": round(ms * 1e-3, 4), "evals_per_ask": round(evals / args.steps, 1), "tell_s": round(t_tells[1], 3),
+           "tell_cold_s": round(t_tells[0], 3),
+           "phases_last_ask": phases, "n_base": acqf_ask.nb, "cells_total": acqf_ask.stats.total_cells,
+           "box_decomposition": acqf_ask.box_path}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(line, ask=ask, outputs=outputs, build=build_provenance())))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     sharded = None
     if dist is not None:
         s2, _ = make_ask_strategy(args.n, args.S, args.raw, args.restarts, world, dist, seed=1)
@@ -737,13 +817,6 @@ def main():
                            "restart problem evaluated by all ranks (all-gather per L-BFGS-B evaluation); "
                            "latency-bound, so not faster than one GPU"}
         del s2
-    acqf_ask = s.last_acqf
-    st_ask = s.last_ask_stats
-    tm = getattr(acqf_ask, "timings", {})
-    phases = {"construction_s": round(tm.get("total", 0.0), 4), "construction": {k: round(v, 4) for k, v in tm.items()},
-              "raw_screening_s": round(st_ask.t_raw, 4), "restarts_s": round(st_ask.t_opt, 4),
-              "optimizer_iterations": st_ask.opt_iters, "evals_last_ask": _ask_evals(s),
-              "driver": st_ask.chunks[0]["driver"] if st_ask.chunks else None}
 
     # per-op device time at the restart batch one rank evaluates per L-BFGS-B iteration, on
     # the candidates the restarts converged to (the scan's work depends on where the
@@ -877,7 +950,7 @@ def main():
                     full = json.load(f)
                 cpu["full_ask_measured"] = dict(full, source=os.path.relpath(full_path, ROOT),
                                                 note="one complete un-extrapolated reference-structure ask on the "
-                                                     "host cores (bench.py --cpu-full-ask)")
+                                                     "host cores (bench.py --full --cpu-full-ask)")
             except (OSError, ValueError):
                 pass
             torch.set_num_threads(1)
@@ -889,36 +962,13 @@ def main():
         t_post = gp_posterior_ms(device, gp=gp_ask)
         cfg1 = None if args.no_config1 else config1_loop()
         out = {
-            "metric": "QnehviStrategy.ask() candidates/sec + GP posterior ms, n=512 d=6 m=5",
-            "value": round(value, 1),
-            "unit": "candidates/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (DTLZ2 d=6 m=5 train set; GPs fitted on device by tell())",
-            "config": {"workload": "full QnehviStrategy.ask() of BASELINE configs[3] (config 4): DTLZ2(d=6,m=5), "
-                                   f"n_train={args.n}, S={args.S} MC samples, {args.raw} raw Sobol candidates + "
-                                   f"{args.restarts} L-BFGS-B restarts, q=1; value = (raw + optimiser "
-                                   "evaluations x batch) / ask wall time, SURVEY.md §8(d)",
-                       "n_train": args.n, "d": args.d, "m": args.m, "mc_samples": args.S, "raw_samples": args.raw,
-                       "restarts": args.restarts, "batch_limit": args.restarts,
-                       "parallelism": (f"replicas: {world} ranks, one full ask each (seeds 1..{world}), no "
-                                       "collective in the timed region; the single ask sharded over the ranks in "
-                                       "sharded_ask" if world > 1 else "1 rank")},
+            **line,
             "roofline": roof,
             "kernels": kernels_r,
             "kernel_ms": {k: round(v, 4) for k, v in kt_r.items()},
             "kernel_ms_method": f"{how} of 10 launches per op between HIP events (torch current stream), "
                                 f"batch {b_r}: {xr_note}",
-            "ask": {"ask_s": round(ms * 1e-3, 4), "evals_per_ask": round(evals / args.steps, 1), "tell_s": round(t_tells[1], 3),
-                    "tell_cold_s": round(t_tells[0], 3),
-                    "phases_last_ask": phases, "n_base": acqf_ask.nb, "cells_total": sum_cells_r,
-                    "box_decomposition": acqf_ask.box_path},
+            "ask": ask,
             "sharded_ask": sharded,
             "eval_pass": eval_pass,
             "qlognehvi": qlog,
@@ -929,6 +979,7 @@ def main():
                              "fitted model), 1024 test points, mean+var, HIP events",
                              "config2_ms": round(gp_posterior_ms(device), 4)},
             "config1": cfg1,
+            "outputs": outputs,
             "build": build_provenance(),
         }
         print(json.dumps(out))

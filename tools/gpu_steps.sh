@@ -12,8 +12,8 @@
 #               -> <tag>/ask_timeline.json
 #   planprobe   tools/plan_setup_probe.py (restart plan creation / first / warm evaluation)
 #   hostprof    tools/ask_host_profile.py (cProfile of 5 warm asks)
-#   benchq      python bench.py --no-cpu-baseline --no-eval-pass (the ask line only)
-#   benche      python bench.py --no-cpu-baseline --no-config1 (ask line + evaluation pass + qLog)
+#   benchq      python bench.py --full --no-cpu-baseline --no-eval-pass (the ask line, restart-batch kernels, posterior, config 1)
+#   benche      python bench.py --full --no-cpu-baseline --no-config1 (ask line + evaluation pass + qLog)
 #   kmatab      bench_kmat.py with the shipped library and everest_amd/_lib_ab, twice interleaved
 #   kmatprof    bench_kmat.py with EVR_KMAT_PROF builds in everest_amd/_libkm{1,2,3} (1: no kernel evaluation,
 #               2: no stores, 3: neither, 4: staging only, 8: staging + norms + MFMA; KMAT_PROFS picks) beside
@@ -38,10 +38,10 @@
 #   hpdump      tools/hp_state_dump.py (config-3 state + device values for tools/hp_truth.py) -> <tag>/hp_state.json
 #   fill        tools/_fill_probe (write-bandwidth ceiling of the 33.5 MB config-5 output: 8 / 16 / 32 B
 #               per lane, cached / non-temporal; hipcc -O3 tools/micro/fill_probe.hip -o tools/_fill_probe)
-#   bench       python bench.py (the driver's default command)
+#   bench       python bench.py --full (every leg of the benchmark)
 #   prof        rocprofv3 --kernel-trace --stats of the bench command
 #   fitprof     the same over tools/fit_probe.py (tell(): the MLL plan's kernels per round)
-#   cpufull     bench.py --cpu-full-ask (one full reference-structure ask on the host cores)
+#   cpufull     bench.py --full --cpu-full-ask (one full reference-structure ask on the host cores)
 #   qsprof      per-workgroup phase stamps of qs_bwd at the bench shape (tools/_qs_prof: hipcc
 #               --offload-arch=gfx950 -O3 -std=c++17 -DEVR_QS_PROF tools/qs_prof.hip -o tools/_qs_prof)
 #   cholprof    phase cycles + result digest of the 64x64 diagonal factor (tools/_chol_prof_pair:
@@ -72,13 +72,13 @@ for st in "$@"; do
       run asktl_parse 60 python tools/ask_timeline.py --analyse "$OUT/asktl" "$OUT/asktl_trace.log" && cp "$OUT/asktl_parse.log" "$OUT/ask_timeline.json" ;;
     hpdump) run hpdump 300 python tools/hp_state_dump.py "$OUT/hp_state.json" ;;
     hpeval) run hpeval 300 python tools/hp_eval.py "$OUT/hp_eval.json" ;;
-    benchsplit) EVR_ROOT=split run benchsplit 600 python bench.py --no-cpu-baseline --no-eval-pass ;;
-    benchfused) EVR_ROOT=fused run benchfused 600 python bench.py --no-cpu-baseline --no-eval-pass ;;
+    benchsplit) EVR_ROOT=split run benchsplit 600 python bench.py --full --no-cpu-baseline --no-eval-pass ;;
+    benchfused) EVR_ROOT=fused run benchfused 600 python bench.py --full --no-cpu-baseline --no-eval-pass ;;
     fill) run fill 60 tools/_fill_probe && cp "$OUT/fill.log" "$OUT/fill.json" ;;
     planprobe) run planprobe 300 python tools/plan_setup_probe.py ;;
     hostprof) run hostprof 300 python tools/ask_host_profile.py ;;
-    benchq) run benchq 600 python bench.py --no-cpu-baseline --no-eval-pass ;;
-    benche) run benche 600 python bench.py --no-cpu-baseline --no-config1 ;;
+    benchq) run benchq 600 python bench.py --full --no-cpu-baseline --no-eval-pass ;;
+    benche) run benche 600 python bench.py --full --no-cpu-baseline --no-config1 ;;
     kmat) KMAT_CASES=cfg5_n2048_d32,cfg5_train_sym,n2048_d6,fit_train_n512 run kmat 300 python tools/bench_kmat.py && cp "$OUT/kmat.log" "$OUT/kmat.json" ;;
     kmatab)
       for i in 1 2; do
@@ -130,10 +130,10 @@ for st in "$@"; do
       run sq20_parse 60 python tools/pmc_sq.py "$OUT/sq20" "$OUT/sq_counters.json" ;;
     kdwwaves) EVR_LIB_PATH=everest_amd/_libkdprof/libeverest_amd.so run kdwwaves 300 python tools/kdw_waves.py ;;
     kdwaves) EVR_LIB_PATH=everest_amd/_libprof/libeverest_amd.so run kdwaves 300 python tools/kd3_waves.py ;;
-    bench) run bench 900 python bench.py ;;
+    bench) run bench 900 python bench.py --full ;;
     fitprof) run fitprof 300 rocprofv3 --kernel-trace --stats -d "$OUT/fitprof" -o run --output-format csv -- python tools/fit_probe.py ;;
-    prof) run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --no-cpu-baseline --steps 10 ;;
-    cpufull) run cpufull 1100 python bench.py --no-eval-pass --steps 2 --warmup 1 --cpu-full-ask "$OUT/cpu_full_ask.json" ;;
+    prof) run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --full --no-cpu-baseline --steps 10 ;;
+    cpufull) run cpufull 1100 python bench.py --full --no-eval-pass --steps 2 --warmup 1 --cpu-full-ask "$OUT/cpu_full_ask.json" ;;
     qsprof) run qsprof 60 tools/_qs_prof && run qsprof_tail 60 tools/_qs_prof tail ;;
     cholprof) run cholprof_pair 60 tools/_chol_prof_pair ;;
     *) echo "unknown step $st"; exit 2 ;;
