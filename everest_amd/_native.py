@@ -54,6 +54,10 @@ class EvrQnGeneral(ctypes.Structure):
         ("zq", c_void_p),
     ]
 
+class EvrNei(ctypes.Structure):
+    _fields_ = [
+        ("log", c_int), ("tau_relu", c_double), ("tau_max", c_double), ("best", c_void_p), ("best_stride", c_int),
+    ]
 
 
 _SIGS = {
@@ -160,6 +164,12 @@ _SIGS = {
                                     POINTER(EvrQnehviModel), c_int, c_int], ctypes.c_longlong),
     "evr_qlog_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnehviState), POINTER(EvrQnGeneral),
                        POINTER(EvrQnehviModel), c_int] + [c_void_p] * 5, c_int),
+    "evr_nei_scan": ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_double,
+                      c_double, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "evr_qnei_workspace_doubles": ([POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel), c_int,
+                                    c_int], c_longlong),
+    "evr_qnei_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
+                       POINTER(EvrNei), c_int] + [c_void_p] * 5, c_int),
     "evr_objective_general": ([c_void_p, c_int, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 4, c_int),
     "evr_objective_weights": ([c_void_p, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 3, c_int),
     "evr_cells_kd_limits": ([c_int, c_int, c_int, c_void_p], c_int),

@@ -969,6 +969,243 @@ class QEIJoint(QEHVI):
         self.a, self.b = float(obj_a), float(obj_b)
 
 
+TAU_MAX_SO = 1e-2   # [upstream] botorch.acquisition.logei.TAU_MAX (single-objective log EI family)
+
+
+class _NeiAcqf(_BoxHviAcqf):
+    """Evaluation side of the single-objective improvement acquisitions (QNEI, QLogNEI,
+    QLogEI): the general chain at one output with the improvement scan of nei_scan.hip
+    between the joint samples and their adjoint (evr_qnei_eval) — no cells, no subsets.
+    Subclasses set gp, dev, S, M, nb and the incumbent(s) ``best`` and call _finish.
+    Pending points ([upstream] concatenate_pending_points) join every candidate's joint
+    batch; the graph-captured native plan does not cover these acquisitions (the optimiser
+    drives them through eval_host)."""
+
+    @property
+    def supports_plan(self) -> bool:
+        return False
+
+    def _finish(self, obj_a: float, obj_b: float, no_h: bool, log: bool, tau_relu: float, tau_max: float,
+                X_pending_raw):
+        gp = self.gp
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        if log and not (tau_relu > 0 and tau_max > 0):
+            raise ValueError("tau_relu and tau_max must be positive")
+        self.m, self.n, self.nk = 1, gp.n, gp.n
+        self.a, self.b = float(obj_a), float(obj_b)
+        self.log_acqf = bool(log)      # log values may be negative: optimize_acqf uses initialize_q_batch
+        self.tau_relu, self.tau_max = float(tau_relu), float(tau_max)
+        self.spec = ops.GeneralSpec(1, [(0, ops.OBJ_AFFINE, self.a, self.b)])
+        self.X_pending = None
+        if X_pending_raw is not None and np.asarray(X_pending_raw).shape[0] > 0:
+            self.X_pending = torch.as_tensor(np.asarray(X_pending_raw, dtype=np.float64).reshape(-1, gp.d), **f64)
+        self.n_pending = 0 if self.X_pending is None else int(self.X_pending.shape[0])
+        self.Xk = gp.Xn
+        self.Rr = gp.n + self.nb + (0 if no_h else self.S) + 1
+        self.state = ops.model_state(gp.n, self.nb, self.S, gp.const, gp.ym, gp.ys, gp.kxx, no_h=no_h)
+        self._lo_c = gp.lo.to(torch.float64).contiguous()
+        self._scale_c = gp.inv_range.to(torch.float64).contiguous()
+        self.model = _native.EvrQnehviModel(n=gp.n, d=gp.d, kind=gp.kind, Xn=self.Xk.data_ptr(),
+                                            lengthscales=gp.ls.data_ptr(), shift=self._lo_c.data_ptr(),
+                                            scale=self._scale_c.data_ptr(), M=self.M.data_ptr())
+        self.best = self.best.to(**f64).reshape(-1).contiguous()
+        self.nei = ops.nei_struct(log, tau_relu, tau_max, self.best)
+        self._zq_cache = {}
+        self._plans = {}
+        torch.cuda.synchronize(self.dev)
+
+    def _pending_rows(self) -> Optional[torch.Tensor]:
+        return self.X_pending
+
+    def _joint(self, X: torch.Tensor) -> torch.Tensor:
+        """b x q x d candidates -> b x (q + n_pending) x d joint batches."""
+        Xp = self.X_pending
+        if Xp is not None:
+            X = torch.cat([X, Xp.unsqueeze(0).expand(X.shape[0], Xp.shape[0], X.shape[2])], 1)
+        if X.shape[1] > ops.QNG_MAX_Q:
+            raise ValueError(f"joint batch of {X.shape[1]} points (q + pending) exceeds the device limit of "
+                             f"{ops.QNG_MAX_Q}")
+        return X
+
+    def _general(self, X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
+        """X: b x q x d -> (acq (b), dX b x q x d | None) through evr_qnei_eval."""
+        b, q, d = X.shape
+        X = self._joint(X)
+        qq = X.shape[1]
+        g = self.spec.struct(qq, self._zq(qq))
+        acq, dX = ops.qnei_eval(self.state, g, self.model, self.nei, X.reshape(b * qq, d).contiguous(), backward,
+                                gout)
+        if dX is not None:
+            dX = dX.view(b, qq, d)[:, :q].contiguous()
+        return acq, dX
+
+    def _torch_acq(self, q: int, fast: bool = False):
+        """The torch.classes.everest_amd.QneiAcq behind torch.ops.everest_amd.qnei_*."""
+        from . import torch_ops
+
+        torch_ops.load()
+        acq = self.__dict__.get("_torch_nei")
+        if acq is None:
+            def raw(st):
+                return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8)
+            acq = torch.classes.everest_amd.QneiAcq(raw(self.state), raw(self.model), self.log_acqf, self.tau_relu,
+                                                    self.tau_max, self.best, self.a, self.b, self._device_tensors())
+            self._torch_nei = acq
+        done = self.__dict__.setdefault("_torch_nei_q", set())
+        if q not in done:
+            acq.set_samples(int(q), self._zq(q))
+            done.add(q)
+        return acq
+
+    def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        """X (b x q x d, or b x d for q = 1) -> acq (b), differentiable through the device
+        backward (torch.ops.everest_amd.qnei_forward / qnei_forward_backward)."""
+        from .torch_ops import QneiFunction
+
+        X3 = self._joint(self._split(X)[0]).contiguous()
+        return QneiFunction.apply(X3, self._torch_acq(X3.shape[1]))
+
+
+class QNEI(_NeiAcqf):
+    """Device qNEI — [upstream] qNoisyExpectedImprovement as built by
+    get_acquisition_function("qNEI") from SoboStrategy._get_acqfs
+    (bofire/strategies/predictives/sobo.py:51-90; cache_root = True):
+
+        acq = mean_s max_i (g(y_si) - best_s)_+,   best_s = max_k g(Y_base[s, k]),
+
+    Y_base = mu_b + L_base z_base the joint draw at the (pruned) baseline (psd_safe_cholesky,
+    3 tries) and the q (+ pending) new points sampled conditionally on it
+    (sample_cached_cholesky, 6-rung jitter ladder on the new block): the QNEHVI operator
+    M = [L^-1; G; H^T; alpha^T] at one output, built here from the same ops without cells.
+    The new points' base samples are rows nb .. nb+q-1 of the (nb+q)-dimensional Sobol draw of
+    the sampler seed.
+
+    prune_baseline: [upstream] prune_inferior_points — ``prune_samples`` Sobol-normal joint
+    draws over the baseline rows, keep the rows that are the arg-max of g in at least one
+    draw (max_frac = 1).  The order in which the reference draws the prune and sampler seeds
+    (and the draws' scrambling) cannot be verified offline; SoboStrategy follows
+    MoboStrategy's qNEHVI branch (prune seed first)."""
+
+    _LOG = False
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, X_baseline_raw: np.ndarray, obj_a: float, obj_b: float,
+                 S: int = 512, sampler_seed: int = 0, prune_baseline: bool = True, prune_seed: int = 0,
+                 prune_samples: int = 2048, z_prune: Optional[torch.Tensor] = None,
+                 X_pending_raw: Optional[np.ndarray] = None, tau_relu: float = TAU_RELU,
+                 tau_max: float = TAU_MAX_SO):
+        if gp.B != 1:
+            raise ValueError(f"{type(self).__name__} takes a single-output model")
+        dev = gp.device
+        self.gp, self.dev, self.S = gp, dev, int(S)
+        self.sampler_seed = int(sampler_seed)
+        n, S_ = gp.n, self.S
+        f64 = dict(dtype=torch.float64, device=dev)
+        a_t = torch.tensor([float(obj_a)], **f64)
+        b_t = torch.tensor([float(obj_b)], **f64)
+        # baseline rows -> training rows (first exact match of the transformed inputs)
+        first = {}
+        for i, row in enumerate(map(tuple, np.asarray(X_train_raw, dtype=np.float64))):
+            first.setdefault(row, i)
+        try:
+            base_rows = np.array([first[tuple(r)] for r in np.asarray(X_baseline_raw, dtype=np.float64)],
+                                 dtype=np.int64)
+        except KeyError as e:
+            raise ValueError("qNEI: every baseline point must be a training point of the model") from e
+        if base_rows.shape[0] == 0:
+            raise ValueError("qNEI needs a non-empty baseline")
+        # joint posterior at the training inputs, shared by prune and baseline
+        K = gp.kernel_train(noise=False)                                    # 1 x n x n
+        mu_t = ops.gemm(K, gp.alpha.unsqueeze(-1))[..., 0]
+        mu_train = gp.ym[:, None] + gp.ys[:, None] * (gp.const[:, None] + mu_t)
+        A = ops.gemm(gp.Linv, K)                                            # L^-1 K
+        Sig = ops.gemm(A, A, transA=True, alpha=-1.0, beta=1.0, out=K)      # K - A^T A (in place)
+        ys2 = (gp.ys ** 2).contiguous()
+        ops.scale_batched(Sig, ys2)
+        self.prune_counts = None
+        if prune_baseline:
+            cand = torch.as_tensor(base_rows, device=dev)
+            nc = int(cand.shape[0])
+            Lp, _, _ = ops.cholesky(Sig[:, cand][:, :, cand].contiguous(), 1e-8, 3)
+            if z_prune is None:
+                Zp = sobol_base_samples(prune_samples, nc, 1, prune_seed, dev)          # 1 x nc x S'
+            else:
+                Zp = z_prune.to(**f64).reshape(-1, nc, 1).permute(2, 1, 0).contiguous()
+            Op = ops.objective_affine(ops.gemm(Lp, Zp), mu_train[:, cand].contiguous(), a_t, b_t)
+            # one objective: "not dominated" is "the arg-max of the draw"
+            _, counts = ops.pareto_mask(Op, torch.full((1,), -math.inf, **f64), dedup=False, want_mask=False,
+                                        want_counts=True)
+            self.prune_counts = counts.cpu().numpy()
+            base_rows = base_rows[np.nonzero(self.prune_counts)[0]]
+        nb = int(base_rows.shape[0])
+        self.nb, self.base_rows = nb, base_rows
+        idx = torch.as_tensor(base_rows, device=dev)
+        # baseline root, draw and per-sample incumbent
+        self.L_base, self.base_jitter, _ = ops.cholesky(Sig[:, idx][:, :, idx].contiguous(), 1e-8, 3)
+        Zb = sobol_base_samples(S_, nb, 1, sampler_seed, dev)                           # 1 x nb x S
+        self._Zb = Zb
+        Ob = ops.objective_affine(ops.gemm(self.L_base, Zb), mu_train[:, idx].contiguous(), a_t, b_t)
+        self.best = Ob[0].amax(0)                                                       # S
+        # operator M = [L^-1; G; H^T; alpha^T], G = s^2 L_base^-1 (P - A_b^T L^-1), H = G^T Z_base
+        Rr = n + nb + S_ + 1
+        M = torch.empty(1, Rr, n, **f64)
+        M[:, :n].copy_(gp.Linv)
+        E = ops.gemm(A[:, :, idx].contiguous(), gp.Linv, transA=True, alpha=-1.0)
+        ops.add_selection(E, idx.to(torch.int32), None)
+        ops.scale_batched(E, ys2)
+        ops.trsm(self.L_base, E)
+        M[:, n:n + nb].copy_(E)
+        ops.gemm_into(M[:, n + nb:n + nb + S_], Zb, E, transA=True)
+        M[:, Rr - 1].copy_(gp.alpha)
+        self.M = M
+        self._finish(obj_a, obj_b, False, self._LOG, tau_relu, tau_max, X_pending_raw)
+
+    def z_base_host(self) -> torch.Tensor:
+        """The baseline base samples (S x nb x 1, host), the oracle's layout."""
+        return self._Zb.permute(2, 1, 0).cpu().contiguous()
+
+    def _draw_zq(self, q: int) -> torch.Tensor:
+        """Rows nb .. nb+q-1 of the (nb+q)-dimensional draw of the sampler seed."""
+        return ops.sobol_normal(self.S, self.nb + q, self.sampler_seed, self.dev, d0=self.nb, nd=q)
+
+
+class QLogNEI(QNEI):
+    """Device qLogNEI (fat = True) — [upstream] qLogNoisyExpectedImprovement, SoboStrategy's
+    default acquisition (bofire/data_models/strategies/predictives/sobo.py:16-18): the QNEI
+    construction with the log scan
+    acq = logmeanexp_s fatmax_i(log fatplus(g(y_si) - best_s; tau_relu); tau_max)."""
+
+    _LOG = True
+
+
+class QLogEI(_NeiAcqf):
+    """Device qLogEI (fat = True) — [upstream] qLogExpectedImprovement: the log scan over plain
+    joint samples y = mu + chol(Sigma_qq) z (M = [L^-1; alpha^T], no H^T rows; the S x (q +
+    n_pending) Sobol-normal draw of the sampler seed) with the scalar incumbent best_f = max
+    over X_train of g(posterior mean), as QEI / QEIJoint compute it.  ``log=False`` evaluates
+    qEI's own integrand mean_s max_i (g - best_f)_+ through the same chain."""
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, obj_a: float, obj_b: float, S: int = 512,
+                 seed: int = 0, X_pending_raw: Optional[np.ndarray] = None, tau_relu: float = TAU_RELU,
+                 tau_max: float = TAU_MAX_SO, log: bool = True):
+        if gp.B != 1:
+            raise ValueError("QLogEI takes a single-output model")
+        self.gp, self.dev, self.S, self.nb = gp, gp.device, int(S), 0
+        self.sampler_seed = int(seed)
+        Xt = torch.as_tensor(np.asarray(X_train_raw, dtype=np.float64), device=self.dev)
+        mean, _ = gp.posterior(Xt)
+        self.best_f = float((float(obj_a) * mean[0] + float(obj_b)).max().item())
+        self.best = torch.tensor([self.best_f], dtype=torch.float64, device=self.dev)
+        self.M = gp.M
+        self._finish(obj_a, obj_b, True, log, tau_relu, tau_max, X_pending_raw)
+
+    def z_base_host(self) -> None:
+        """No baseline draw (plain joint sampling)."""
+        return None
+
+    def _draw_zq(self, q: int) -> torch.Tensor:
+        return ops.sobol_normal(self.S, q, self.sampler_seed, self.dev)
+
+
 class QEI:
     """Device qEI (q = 1, one output) — [upstream] qExpectedImprovement as built by
     ``get_acquisition_function("qEI", ...)`` from SoboStrategy._get_acqfs

@@ -286,9 +286,98 @@ at::Tensor qnehvi_backward(const AcqPtr& acq, const at::Tensor& X, const at::Ten
   return dX * g.view(shape);
 }
 
+// ---------------------------------------------------------------------------------------
+// The acquisition behind torch.ops.everest_amd.qnei_*: qNEI / qLogNEI / qLogEI through
+// evr_qnei_eval.  Owns copies of the state / model structs, the incumbent(s) and the base
+// samples per joint batch size, and references to the device tensors they point into.
+// ---------------------------------------------------------------------------------------
+struct QneiAcq : torch::CustomClassHolder {
+  evr_qnehvi_state stm{};
+  evr_qnehvi_model md{};
+  evr_nei nei{};
+  int oo = 0, ok = EVR_OBJ_AFFINE;
+  double p0 = 1.0, p1 = 0.0;
+  at::Tensor best;
+  std::vector<at::Tensor> keep;
+  std::map<int64_t, at::Tensor> zqs;
+  int64_t n_evals = 0;
+
+  QneiAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
+          const at::Tensor& best_, double obj_a, double obj_b, std::vector<at::Tensor> keep_)
+      : p0(obj_a), p1(obj_b), keep(std::move(keep_)) {
+    stm = QnehviAcq::from_bytes<evr_qnehvi_state>(stm_b, "model-side state");
+    md = QnehviAcq::from_bytes<evr_qnehvi_model>(md_b, "model");
+    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m == 1,
+                "QneiAcq: inconsistent single-output model");
+    best = dev64(best_, "best");
+    TORCH_CHECK(best.numel() == 1 || best.numel() == stm.S, "QneiAcq: best needs 1 or S values");
+    nei.log = log_ ? 1 : 0;
+    nei.tau_relu = tau_relu;
+    nei.tau_max = tau_max;
+    nei.best = best.data_ptr<double>();
+    nei.best_stride = best.numel() == 1 ? 0 : 1;
+  }
+
+  void set_samples(int64_t q, const at::Tensor& zq) {
+    TORCH_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "QneiAcq.set_samples: q = ", q, " outside 1..", EVR_QNG_MAX_Q);
+    auto z = dev64(zq, "zq");
+    TORCH_CHECK(z.numel() == (int64_t)stm.S * q, "QneiAcq.set_samples: zq must be S x q");
+    zqs[q] = z;
+  }
+
+  std::tuple<at::Tensor, at::Tensor> eval(const at::Tensor& X_, bool backward) {
+    auto X = dev64(X_, "X");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+    hipStream_t s = cur_stream();
+    TORCH_CHECK(X.dim() == 3 && X.size(2) == md.d, "qnei: X must be b x q x d");
+    const int64_t b = X.size(0), q = X.size(1);
+    auto it = zqs.find(q);
+    TORCH_CHECK(it != zqs.end(), "qnei: no base samples set for q = ", q);
+    evr_qn_general g{};
+    g.q = (int)q;
+    g.m_obj = 1;
+    g.obj_out = &oo;
+    g.obj_kind = &ok;
+    g.obj_p0 = &p0;
+    g.obj_p1 = &p1;
+    g.zq = it->second.data_ptr<double>();
+    auto acq = at::empty({b}, X.options());
+    at::Tensor dX = backward ? at::empty_like(X) : at::Tensor();
+    if (b == 0) return {acq, dX};
+    auto work = scratch(evr_qnei_workspace_doubles(&stm, &g, &md, (int)b, backward), X);
+    check(evr_qnei_eval(s, &stm, &g, &md, &nei, (int)b, X.data_ptr<double>(), nullptr, work.data_ptr<double>(),
+                        acq.data_ptr<double>(), backward ? dX.data_ptr<double>() : nullptr),
+          "qnei_eval");
+    ++n_evals;
+    return {acq, dX};
+  }
+
+  int64_t evals() const { return n_evals; }
+};
+
+using NeiPtr = c10::intrusive_ptr<QneiAcq>;
+
+at::Tensor qnei_forward(const NeiPtr& acq, const at::Tensor& X) { return std::get<0>(acq->eval(X, false)); }
+
+std::tuple<at::Tensor, at::Tensor> qnei_forward_backward(const NeiPtr& acq, const at::Tensor& X) {
+  return acq->eval(X, true);
+}
+
+at::Tensor qnei_backward(const NeiPtr& acq, const at::Tensor& X, const at::Tensor& grad_out_) {
+  auto g = dev64(grad_out_, "grad_out");
+  auto dX = std::get<1>(acq->eval(X, true));
+  TORCH_CHECK(g.numel() == dX.size(0), "qnei_backward: grad_out must have one entry per candidate");
+  return dX * g.view({dX.size(0), 1, 1});
+}
+
 }  // namespace
 
 TORCH_LIBRARY(everest_amd, m) {
+  m.class_<QneiAcq>("QneiAcq")
+      .def(torch::init<at::Tensor, at::Tensor, bool, double, double, at::Tensor, double, double,
+                       std::vector<at::Tensor>>())
+      .def("set_samples", &QneiAcq::set_samples)
+      .def("evals", &QneiAcq::evals);
   m.class_<QnehviAcq>("QnehviAcq")
       .def(torch::init<at::Tensor, at::Tensor, at::Tensor, bool, bool, std::vector<at::Tensor>>())
       .def("set_general", &QnehviAcq::set_general)
@@ -302,6 +391,9 @@ TORCH_LIBRARY(everest_amd, m) {
   m.def("qnehvi_forward(__torch__.torch.classes.everest_amd.QnehviAcq acq, Tensor X) -> Tensor");
   m.def("qnehvi_forward_backward(__torch__.torch.classes.everest_amd.QnehviAcq acq, Tensor X) -> (Tensor, Tensor)");
   m.def("qnehvi_backward(__torch__.torch.classes.everest_amd.QnehviAcq acq, Tensor X, Tensor grad_out) -> Tensor");
+  m.def("qnei_forward(__torch__.torch.classes.everest_amd.QneiAcq acq, Tensor X) -> Tensor");
+  m.def("qnei_forward_backward(__torch__.torch.classes.everest_amd.QneiAcq acq, Tensor X) -> (Tensor, Tensor)");
+  m.def("qnei_backward(__torch__.torch.classes.everest_amd.QneiAcq acq, Tensor X, Tensor grad_out) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(everest_amd, CUDA, m) {
@@ -312,4 +404,7 @@ TORCH_LIBRARY_IMPL(everest_amd, CUDA, m) {
   m.impl("qnehvi_forward", &qnehvi_forward);
   m.impl("qnehvi_forward_backward", &qnehvi_forward_backward);
   m.impl("qnehvi_backward", &qnehvi_backward);
+  m.impl("qnei_forward", &qnei_forward);
+  m.impl("qnei_forward_backward", &qnei_forward_backward);
+  m.impl("qnei_backward", &qnei_backward);
 }

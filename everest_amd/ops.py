@@ -511,6 +511,70 @@ def qlog_eval(stm: EvrQnehviState, sth: EvrQnehviState, g: EvrQnGeneral, model: 
     return acq, dX
 
 
+def model_state(n, nb, S, c, ym, ys, kxx, no_h: bool = False) -> EvrQnehviState:
+    """Model-side state of a single-output chain without cells (evr_qnei_eval): the operator
+    layout (n, nb, S, no_h) and the output's constant / standardisation / prior variance."""
+    st = EvrQnehviState()
+    st.n, st.nb, st.S, st.m = int(n), int(nb), int(S), 1
+    st.no_h = int(bool(no_h))
+    st.c, st.ym, st.ys, st.kxx = c.data_ptr(), ym.data_ptr(), ys.data_ptr(), kxx.data_ptr()
+    return st
+
+
+def nei_struct(log: bool, tau_relu: float, tau_max: float, best: torch.Tensor) -> "_native.EvrNei":
+    """evr_nei over ``best`` (device; S per-sample incumbents, or one value: stride 0)."""
+    best = _dev(best, "best")
+    nei = _native.EvrNei()
+    nei.log, nei.tau_relu, nei.tau_max = int(bool(log)), float(tau_relu), float(tau_max)
+    nei.best, nei.best_stride = best.data_ptr(), 0 if best.numel() == 1 else 1
+    return nei
+
+
+def nei_scan(Y: torch.Tensor, q: int, best: torch.Tensor, obj_a: float, obj_b: float, log: bool = False,
+             tau_relu: float = 1e-6, tau_max: float = 1e-2, flags: Optional[torch.Tensor] = None,
+             gout: Optional[torch.Tensor] = None, backward: bool = False):
+    """Improvement scan alone (evr_nei_scan): Y S x (b*q) joint samples (point i of candidate c
+    at column c*q + i), best S incumbents or one -> (acq (b), dY S x (b*q) | None)."""
+    Y, best = _dev(Y, "Y"), _dev(best, "best")
+    S, bq = Y.shape
+    q = int(q)
+    if q < 1 or bq % q:
+        raise ValueError(f"{bq} columns are not a multiple of q = {q}")
+    if best.numel() not in (1, S):
+        raise ValueError(f"best needs 1 or S = {S} values, got {best.numel()}")
+    b = bq // q
+    flags = None if flags is None else _dev(flags, "flags", torch.int32)
+    gout = None if gout is None else _dev(gout, "gout")
+    if (flags is not None and flags.numel() != b) or (gout is not None and gout.numel() != b):
+        raise ValueError("flags / gout need one entry per candidate")
+    acq = torch.empty(b, dtype=torch.float64, device=Y.device)
+    dY = torch.empty_like(Y) if backward else None
+    call("evr_nei_scan", _stream(), q, int(bool(log)), S, b, Y.data_ptr(), best.data_ptr(),
+         0 if best.numel() == 1 else 1, float(obj_a), float(obj_b), float(tau_relu), float(tau_max), _p(flags),
+         _p(gout), acq.data_ptr(), _p(dY))
+    return acq, dY
+
+
+def qnei_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviModel", nei: "_native.EvrNei",
+              X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
+    """qNEI / qLogNEI / qLogEI (evr_qnei_eval): X (b*q) x d raw candidates -> acq (b)
+    [, dX (b*q) x d]."""
+    X = _dev(X, "X")
+    q = int(g.q)
+    bq, d = X.shape
+    if bq % q:
+        raise ValueError(f"{bq} rows are not a multiple of q = {q}")
+    b = bq // q
+    lib = _native.load()
+    work = _workspace(lib.evr_qnei_workspace_doubles(ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), b,
+                                                     int(backward)), X.device)
+    acq = torch.empty(b, dtype=torch.float64, device=X.device)
+    dX = torch.empty_like(X) if backward else None
+    call("evr_qnei_eval", _stream(), ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), ctypes.byref(nei), b,
+         X.data_ptr(), _p(None if gout is None else _dev(gout, "gout")), work.data_ptr(), acq.data_ptr(), _p(dX))
+    return acq, dX
+
+
 class QnehviPlan:
     """Native evaluation plan of the whole qNEHVI chain for a fixed batch size b
     (qnehvi_plan.hip): persistent device buffers X (b x d), out = [acq (b) | dX (b x d)] and

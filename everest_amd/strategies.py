@@ -20,7 +20,8 @@ import torch
 
 from . import data_models as dm
 from . import ops
-from .acquisition import QEHVI, QEI, QEIJoint, QLogEHVI, QLogNEHVI, QNEHVI, prefetch_scramble
+from .acquisition import (QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI,
+                          prefetch_scramble)
 from .data_models.domain import CloseToTargetObjective, MaximizeObjective, MinimizeObjective
 from .optim import (OptimizeStats, hit_and_run, host_values, optimize_acqf, optimize_acqf_mixed,
                     prefetch_raw_samples)
@@ -728,7 +729,8 @@ class MoboStrategy(_MultiobjectiveMixin, BotorchStrategy):
 
 
 class SoboStrategy(BotorchStrategy):
-    """bofire/strategies/predictives/sobo.py:40-120 — qEI on the device."""
+    """bofire/strategies/predictives/sobo.py:40-120 — qLogNEI (the data model's default),
+    qNEI, qLogEI and qEI on the device; single output, no output constraints."""
 
     def __init__(self, data_model, dist=None, **kwargs):
         super().__init__(data_model, dist=dist)
@@ -736,15 +738,31 @@ class SoboStrategy(BotorchStrategy):
         self.last_acqf = None
 
     def _get_acqfs(self, n):
-        if not isinstance(self.acquisition_function, dm.qEI):
-            raise NotImplementedError(f"{type(self.acquisition_function).__name__} is out of scope; use qEI()")
+        af = self.acquisition_function
+        if not isinstance(af, (dm.qEI, dm.qLogEI, dm.qNEI, dm.qLogNEI)):
+            raise NotImplementedError(f"{type(af).__name__} is out of scope; use qLogNEI(), qNEI(), qLogEI() or qEI()")
         target = self.domain.outputs.get_by_objective([MaximizeObjective, MinimizeObjective]).features[0]
         if self.model.output_keys.index(target.key) != 0 or len(self.model.output_keys) != 1:
             raise NotImplementedError("single-output SOBO only")
         a, b = target.objective.affine()
         X_train, X_pending = self.get_acqf_input_tensors()
+        S = int(af.n_mc_samples)
+        if isinstance(af, (dm.qNEI, dm.qLogNEI)):
+            # seed order of MoboStrategy's qNEHVI branch: prune seed (when pruning), then sampler seed
+            def draw_seed():
+                return int(torch.randint(0, 1000000, (1,), generator=self.gen).item())
+            prune_seed = draw_seed() if af.prune_baseline else 0
+            sampler_seed = draw_seed()
+            cls = QLogNEI if isinstance(af, dm.qLogNEI) else QNEI
+            acqf = cls(self.model, self.model.X_raw, X_train, a, b, S=S, sampler_seed=sampler_seed,
+                       prune_baseline=af.prune_baseline, prune_seed=prune_seed, X_pending_raw=X_pending)
+            self.last_acqf = acqf
+            return [acqf]
         seed = int(torch.randint(0, 1000000, (1,), generator=self.gen).item())
-        S = int(self.acquisition_function.n_mc_samples)
+        if isinstance(af, dm.qLogEI):
+            acqf = QLogEI(self.model, X_train, a, b, S=S, seed=seed, X_pending_raw=X_pending)
+            self.last_acqf = acqf
+            return [acqf]
         if X_pending is None and n == 1:
             acqf = QEI(self.model, X_train, a, b, S=S, seed=seed)
         else:

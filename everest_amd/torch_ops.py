@@ -11,6 +11,8 @@ AcquisitionFunction.forward protocols called at bofire/strategies/predictives/bo
     torch.ops.everest_amd.qnehvi_forward(acq, X) -> acq values
     torch.ops.everest_amd.qnehvi_forward_backward(acq, X) -> (acq values, dX)
     torch.ops.everest_amd.qnehvi_backward(acq, X, grad_out) -> dX
+    torch.classes.everest_amd.QneiAcq(state, model, log, tau_relu, tau_max, best, a, b, keep)
+    torch.ops.everest_amd.qnei_forward / qnei_forward_backward / qnei_backward   (qNEI, qLogNEI, qLogEI)
 
 No fallback: a missing library raises NativeLibraryError."""
 from __future__ import annotations
@@ -62,3 +64,24 @@ class QnehviFunction(torch.autograd.Function):
         (dX,) = ctx.saved_tensors
         shape = (dX.shape[0],) + (1,) * (dX.dim() - 1)
         return dX * grad_out.reshape(shape), None
+
+
+class QneiFunction(torch.autograd.Function):
+    """acq = qNEI / qLogNEI / qLogEI(X), X b x q x d, through torch.ops.everest_amd.qnei_* on a
+    torch.classes.everest_amd.QneiAcq; as QnehviFunction, one device chain gives the value and
+    the analytic gradient, and backward scales the saved dX by grad_out."""
+
+    @staticmethod
+    def forward(ctx, X: torch.Tensor, acq):
+        ops = load()
+        if ctx.needs_input_grad[0]:
+            a, dX = ops.qnei_forward_backward(acq, X)
+            ctx.save_for_backward(dX)
+            return a
+        ctx.save_for_backward(None)
+        return ops.qnei_forward(acq, X)
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        (dX,) = ctx.saved_tensors
+        return dX * grad_out.reshape(-1, 1, 1), None

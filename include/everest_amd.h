@@ -428,6 +428,40 @@ int evr_objective_general(void* stream, int m_model, int n, int S, const evr_qn_
 int evr_objective_weights(void* stream, int m_model, int n, const evr_qn_general* g, const double* Y, double* G,
                           double* W);
 
+/* ---- single-objective improvement scan: qNEI / qLogNEI / qLogEI (nei_scan.hip) ----------
+ * The step between the joint samples Y of q-point candidates and dY for one output with the
+ * affine objective g = a*y + b ([upstream] qNoisyExpectedImprovement, qLogNoisyExpected-
+ * Improvement, qLogExpectedImprovement as called from bofire/strategies/predictives/
+ * sobo.py:51-90):
+ *   plain (log = 0): acq_c = mean_s max_i (g(y_sci) - best_s)_+
+ *   log   (log = 1): acq_c = logmeanexp_s fatmax_i(log fatplus(g(y_sci) - best_s; tau_relu); tau_max)
+ * Y: S x (b*q), point i of candidate c at column c*q + i.  best: device, S values
+ * (best_stride = 1: the per-sample incumbent of qNEI / qLogNEI) or one value (best_stride =
+ * 0: the scalar best_f of qLogEI / qEI).  flags (nullable, b ints): acq_c = NaN where set.
+ * dY (nullable = forward only): d(sum_c gout_c acq_c)/dY, S x (b*q); gout (nullable, b) = 1.
+ * Plain mode uses the subgradients of evr_qei / evr_qng_eval (strict improvement, first
+ * arg-max).  Forward and backward are ONE launch; results are bitwise reproducible. */
+int evr_nei_scan(void* stream, int q, int log, int S, int b, const double* Y, const double* best,
+                 int best_stride, double obj_a, double obj_b, double tau_relu, double tau_max,
+                 const int* flags, const double* gout, double* acq, double* dY);
+typedef struct {
+  int log;              /* 0: qNEI (plain), 1: qLogNEI / qLogEI */
+  double tau_relu;      /* log mode: fatplus temperature ([upstream] TAU_RELU = 1e-6) */
+  double tau_max;       /* log mode: fatmax temperature ([upstream] logei.TAU_MAX = 1e-2) */
+  const double* best;   /* device: incumbent(s) in objective space */
+  int best_stride;      /* 1: S per-sample values, 0: one value */
+} evr_nei;
+/* Full evaluation modelled on evr_qng_eval: kernel matrix -> projection R = M K_x -> q x q
+ * Gram / jittered Cholesky / joint samples -> evr_nei_scan -> (dX != NULL) analytic backward.
+ * stm: single-output model-side state (m = 1; n, nb, S, no_h, c, ym, ys, kxx; cells unused);
+ * g: q (1..EVR_QNG_MAX_Q), ONE affine objective on output 0, no constraints, zq (device,
+ * S x q).  X: (b*q) x d raw candidates; acq: b; dX: (b*q) x d. */
+long long evr_qnei_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                     const evr_qnehvi_model* md, int b, int backward);
+int evr_qnei_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                  const evr_nei* nei, int b, const double* X, const double* gout, double* work, double* acq,
+                  double* dX);
+
 /* The PyTorch-ROCm operators torch.ops.everest_amd.qnehvi_* (everest_amd/csrc/torch_ops.cpp)
  * take a torch.classes.everest_amd.QnehviAcq: it copies the evr_qnehvi_state /
  * evr_qnehvi_model / evr_qn_general structs, holds references to the device tensors they
