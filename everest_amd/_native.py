@@ -118,6 +118,7 @@ _SIGS = {
     "evr_cells_from_keys": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 5, c_int),
     "evr_hvi_forward_backward": ([c_void_p, POINTER(EvrQnehviState), c_int] + [c_void_p] * 6, c_int),
     "evr_hvi_restart_fb_applies": ([POINTER(EvrQnehviState), c_int], c_int),
+    "evr_hvi_scan_limits": ([c_int, c_int], c_int),
     "evr_hvi_restart_fb": ([c_void_p, POINTER(EvrQnehviState), c_int] + [c_void_p] * 3, c_int),
     "evr_qnehvi_norms_rows": ([POINTER(EvrQnehviState)], c_int),
     "evr_qnehvi_project": ([c_void_p, POINTER(EvrQnehviState), c_int] + [c_void_p] * 5, c_int),

@@ -130,7 +130,11 @@ def _decompose(O: torch.Tensor, ref: torch.Tensor, box_device=None, kd_scan=None
     approx = alpha > 0.0 and m > 2
     if approx and box_device:
         raise ValueError("the device box decomposition is exact only (alpha = 0)")
-    if not approx and (box_device if box_device is not None else ops.box_device_supported(P, m)):
+    # the device cells are compressed over point tables of P + m rows, which every linear scan
+    # stages in LDS: its bound is tighter than the decomposition's own for m <= 5
+    # (an explicit box_device=True is taken at its word, as for the decomposition's own limits)
+    if not approx and (box_device if box_device is not None else
+                       ops.box_device_supported(P, m) and ops.hvi_scan_supported(P + m, m)):
         kd_built = False
         try:
             if kd_scan is False or os.environ.get("EVR_BOX_PIPELINE", "1") == "0":

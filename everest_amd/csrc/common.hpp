@@ -358,7 +358,9 @@ __device__ __forceinline__ double log_tab(double w, const FastLogTabs& T) {
 __device__ __forceinline__ double exp_tab_neg(double x, const FastLogTabs& T) {
   if (x < -745.2) return 0.0;
   constexpr double K64 = 92.33248261689365951;   // 64 / ln 2
-  constexpr double C_HI = 1.08304246962070465088e-02, C_LO = 2.98155597433513719e-12;   // ln2 / 64
+  // ln2 / 64 = C_HI + C_LO to ~1e-30 (C_LO is the remainder of this C_HI: with LN2_LO / 64 the
+  // sum was 2.9e-12 too large and exp(x) off by 2.7e-10 |x| relative)
+  constexpr double C_HI = 1.08304246962070465088e-02, C_LO = 4.20986316660698181e-14;
   const double kd = rint(x * K64);
   const int k = (int)kd;
   const double r = fma(-kd, C_LO, fma(-kd, C_HI, x));

@@ -1484,12 +1484,15 @@ long long hvi_log_workspace(const evr_qnehvi_state* st, int b, int backward);
 int hvi_log_launch(hipStream_t s, const evr_qnehvi_state* st, int b, const double* G, const int* flags,
                    const double* gout, double* work, double* acq, double* dG, bool backward);
 
+// the keyed scans stage a sample's point table (stride rows of m doubles + rank0) in LDS
+static bool hvi_point_table_fits(long long stride, int m) { return stride * (m * 8 + 4) <= 64 * 1024; }
+
 static int hvi_check_state(const evr_qnehvi_state* st) {
   EVR_CHECK(st && st->S >= 1 && st->m >= 1 && st->cell_off, "hvi: bad state");
   if (st->log_hvi) return 0;   // hvi_log_launch checks its own inputs
   EVR_CHECK(st->cell_keys ? (st->cell_pts && st->cell_rank0 && st->pts_stride > 0) : (st->cell_lo && st->cell_hi),
             "hvi: state has neither explicit nor compressed cells");
-  EVR_CHECK(!st->cell_keys || (size_t)st->pts_stride * (st->m * 8 + 4) <= 64 * 1024,
+  EVR_CHECK(!st->cell_keys || hvi_point_table_fits(st->pts_stride, st->m),
             "hvi: point table of %d rows exceeds the LDS budget", st->pts_stride);
   EVR_CHECK(!st->grp_off || (st->cell_keys && st->grp_keys && st->grp_rank && st->grp_box && st->sorted_lo &&
                              st->max_groups >= 0 &&
@@ -1582,6 +1585,11 @@ int evr_hvi_forward_backward(void* stream, const evr_qnehvi_state* st, int b, co
 }
 
 int evr_hvi_restart_fb_applies(const evr_qnehvi_state* st, int b) { return hvi_kdw_applies(st, b) ? 1 : 0; }
+
+int evr_hvi_scan_limits(int stride, int m) {
+  EVR_CHECK(stride > 0 && m >= 1 && m <= 8, "evr_hvi_scan_limits: bad arguments");
+  return hvi_point_table_fits(stride, m) ? 0 : 3;
+}
 
 int evr_hvi_restart_fb(void* stream, const evr_qnehvi_state* st, int b, const double* G, double* sval,
                        double* dG) {

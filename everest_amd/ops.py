@@ -760,6 +760,12 @@ def box_device_supported(n: int, m: int) -> bool:
     return _native.load().evr_box_device_limits(int(n), int(m), None, None) == 0
 
 
+def hvi_scan_supported(stride: int, m: int) -> bool:
+    """The linear HVI scans take compressed cells over point tables of ``stride`` rows (the
+    device box decomposition's output has stride = n + m)."""
+    return _native.load().evr_hvi_scan_limits(int(stride), int(m)) == 0
+
+
 class Cells:
     """Box cells of S samples on the device, ragged by ``off`` (S+1 int32): either explicit
     (``lo``/``hi``, C x m) or compressed (``keys`` C uint64 + per-sample point tables ``pts``

@@ -244,6 +244,10 @@ int evr_hvi_forward_backward(void* stream, const evr_qnehvi_state* st, int b, co
  * (evr_mean_over_samples; the plan folds it into the dX reduction).  _applies: 1 when the
  * state / batch qualifies. */
 int evr_hvi_restart_fb_applies(const evr_qnehvi_state* st, int b);
+/* 0 if the linear scans accept compressed cells whose point tables have `stride` rows (the
+ * bound every evr_hvi_* entry checks: the table is staged in LDS), else 3.  A caller asks
+ * before it chooses the device box decomposition (stride = n + m). */
+int evr_hvi_scan_limits(int stride, int m);
 int evr_hvi_restart_fb(void* stream, const evr_qnehvi_state* st, int b, const double* G, double* sval,
                        double* dG);
 /* gR_j (Rr x b): gradient w.r.t. R_j given dG (chains objective, sampling, L22 ladder) */

@@ -26,7 +26,8 @@ def _front(S, n, m, seed, dup=False, discrete=False):
     return -X                          # maximisation objective, ref -1.1
 
 
-@pytest.mark.parametrize("m,n,S", [(1, 17, 4), (2, 40, 8), (3, 60, 16), (4, 50, 8), (5, 120, 32), (6, 40, 4)])
+@pytest.mark.parametrize("m,n,S", [(1, 17, 4), (2, 40, 8), (3, 60, 16), (4, 50, 8), (5, 120, 32), (6, 40, 4),
+                                   (7, 16, 4), (8, 12, 4)])
 @pytest.mark.parametrize("variant", ["plain", "dup", "discrete"])
 def test_device_box_decomposition_matches_host(m, n, S, variant):
     O = _front(S, n, m, seed=m * 100 + n, dup=variant == "dup", discrete=variant == "discrete")

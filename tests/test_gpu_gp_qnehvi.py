@@ -104,7 +104,8 @@ def _matched_qnehvi(n, d, m, S, seed, prune, nprune=64, alpha=0.0):
     return X, lo, hi, orc, dq, idx
 
 
-@pytest.mark.parametrize("n,d,m,S,prune", [(20, 3, 2, 16, False), (40, 4, 3, 32, True), (60, 6, 5, 16, True)])
+@pytest.mark.parametrize("n,d,m,S,prune", [(20, 3, 2, 16, False), (40, 4, 3, 32, True), (60, 6, 5, 16, True),
+                                           (16, 7, 6, 8, False), (16, 8, 7, 8, True), (12, 9, 8, 8, False)])
 def test_qnehvi_forward_backward_parity(n, d, m, S, prune):
     X, lo, hi, orc, dq, idx = _matched_qnehvi(n, d, m, S, seed=n, prune=prune)
     assert dq.nb == idx.shape[0]

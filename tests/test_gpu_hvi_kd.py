@@ -81,11 +81,9 @@ def test_kd2_bench_size_matches_tiled_scan():
     assert (a1 > 0).sum() > b // 2
 
 
-def test_kd_index_invariants():
-    from everest_amd import ops
-
-    kd, dense, lo, hi, d = _pair(150, 6, 5, 32, seed=2)
-    cells = kd.cells
+def _assert_kd_index_invariants(cells):
+    """Every cell kept exactly once in the kd order, padding, group minima, ascending lower
+    bounds, and lower bounds recovered through the rank index."""
     g = cells.kd
     m = cells.m
     off = cells.off.cpu().numpy()
@@ -111,6 +109,7 @@ def test_kd_index_invariants():
         flat = r.transpose(0, 2, 1).reshape(-1, m)
         assert (flat[C:] == 0x7FFF).all() and (flat[:C] < 0x7FFF).all()
         assert np.array_equal(box[goff[s]:goff[s + 1], :m], r.min(axis=2))
+        assert (box[goff[s]:goff[s + 1], m:] == 0).all()             # slots beyond m always pass
         assert (sv[s][:, 1:] >= sv[s][:, :-1]).all()                 # ascending per objective
     # lower bounds recovered through the rank index equal the decoded cells
     lo_x, _ = cells.explicit()
@@ -120,6 +119,89 @@ def test_kd_index_invariants():
     flat = rank[goff[0]:goff[1]].transpose(0, 2, 1).reshape(-1, m)[:C]
     lo_rank = np.stack([sv[0, j, flat[:, j]] for j in range(m)], 1)
     assert np.array_equal(np.sort(lo_rank, axis=0), np.sort(lo_x[:C], axis=0))
+
+
+def test_kd_index_invariants():
+    kd, dense, lo, hi, d = _pair(150, 6, 5, 32, seed=2)
+    _assert_kd_index_invariants(kd.cells)
+
+
+def _kd_order_raw(cells, max_cells):
+    """evr_cells_kd_order_device on cells with the given max_cells: it sizes the LDS sort
+    buffer and picks the sort-key layout (u32 when max_cells < 8192 and stride < 1023, else
+    u64); the kernel sorts by each sample's own count."""
+    from everest_amd import ops
+
+    S, m, stride = cells.S, cells.m, cells.stride
+    dev = cells.off.device
+    ng = (cells.counts + 15) // 16
+    goff_h = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum(ng, out=goff_h[1:])
+    G = int(goff_h[-1])
+    goff = torch.as_tensor(goff_h.astype(np.int32)).to(dev)
+    keys = torch.zeros(G * 16, dtype=torch.int64, device=dev)
+    rank = torch.zeros(G * m * 16, dtype=torch.int16, device=dev)
+    box = torch.zeros(G * 8, dtype=torch.int16, device=dev)
+    sorted_lo = torch.zeros(S, m, stride, dtype=torch.float64, device=dev)
+    ops.call("evr_cells_kd_order_device", ops._stream(), S, m, stride, cells.off.data_ptr(), goff.data_ptr(),
+             int(max_cells), cells.keys.data_ptr(), cells.pts.data_ptr(), cells.rank0.data_ptr(), keys.data_ptr(),
+             rank.data_ptr(), box.data_ptr(), sorted_lo.data_ptr())
+    return keys, rank, box, sorted_lo
+
+
+@pytest.mark.parametrize("which", ["m5", "m8"])
+def test_kd_u64_sort_keys_equal_u32_bitwise(which):
+    """cells_kd_kernel<M, unsigned long long> against cells_kd_kernel<M, unsigned int> on the
+    same cells (M = 5: the state of test_kd_index_invariants; M = 8: sphere n = 12, S = 8):
+    max_cells = 8192 selects the u64 layout and sizes the LDS for 8192 keys (within the
+    kernel's 96 KB since stride m 10 + 16 <= 32 KB), the true max_cells the u32 layout.  Both
+    orders are the same, so keys, ranks, group minima and sorted lower bounds are equal bit
+    for bit."""
+    from everest_amd import ops
+    from tests import hvi_reference as hr
+
+    if which == "m5":
+        cells = _pair(150, 6, 5, 32, seed=2)[0].cells
+    else:
+        fr = hr.sphere(8, 12, 8, seed=812)
+        O = torch.tensor(np.ascontiguousarray(fr.transpose(2, 1, 0)), device="cuda")
+        cells, built = ops.box_decompose_kd_device(O, torch.full((8,), hr.REF, dtype=torch.float64, device="cuda"))
+        assert built
+    assert cells.max_cells < 8192 and cells.stride < 1023                 # u32 by itself
+    assert cells.stride * cells.m * 10 + 16 <= 32 * 1024 and ops.kd_supported(cells)
+    assert which == "m5" or cells.max_cells > 1024                        # whole-buffer and wave sorts both run
+    k32 = _kd_order_raw(cells, cells.max_cells)
+    k64 = _kd_order_raw(cells, 8192)
+    for a, b in zip(k32, k64):
+        assert torch.equal(a, b)
+    g = cells.kd                                                          # what the pipeline built
+    for a, b in zip(k64, (g.keys, g.rank, g.box, g.sorted_lo)):
+        assert torch.equal(a.reshape(-1), b.reshape(-1)[:a.numel()])
+
+
+@pytest.mark.parametrize("m,n,S", [(3, 1100, 2), (2, 1100, 4)])
+def test_kd_u64_sort_keys_natural(m, n, S):
+    """stride = n + m >= 1023, so evr_box_kd_pipeline sorts with cells_kd_kernel<M, unsigned
+    long long> by itself (M = 3: ~870 cells per sample; M = 2: ~95): box_path device+kd, the
+    index invariants, and hvi_kd2<M> / hvi_kdw<M> / hvi_tiled<M> against the CPU reference at
+    b = 20 within the derived rounding bound (tests/test_gpu_hvi_wide.py)."""
+    from everest_amd import acquisition, ops
+    from tests import hvi_reference as hr
+    from tests import hvi_scan_checks as sc
+
+    fronts = hr.sphere(S, n, m, seed=n + m)
+    assert n + m >= 1023
+    O, ref = sc.dev_fronts(fronts)
+    cells, path = acquisition._decompose(O, ref)
+    assert path == "device+kd" and cells.kd is not None and cells.stride == n + m
+    _assert_kd_index_invariants(cells)
+    Y, ties, R = sc.reference(("u64", m, n, S), fronts, 20)
+    assert np.array_equal(cells.counts, np.asarray(R.counts))
+    worst = sc.Worst()
+    ran = sc.run_paths(cells, R, Y, ties, (20,), worst, True)
+    assert {"kd2", "restart", "tiled-keys", "fwd-kd"} <= ran
+    worst.report(f"hvi u64 kd keys m={m} n={n} S={S} cells<={cells.max_cells}",
+                 hr.rounding_factor(max(R.c_max, cells.max_cells), m))
 
 
 @pytest.mark.parametrize("n,d,m,S,b", [(120, 6, 5, 256, 20), (60, 4, 3, 256, 7), (40, 3, 2, 512, 1),

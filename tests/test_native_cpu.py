@@ -364,3 +364,31 @@ def test_hit_and_run_samples_feasible_and_uniform():
     # seeded: the same seed gives the same samples, another seed others
     assert np.array_equal(Y, hit_and_run(bounds3, [], [([0, 1, 2], [1.0, 1.0, 1.0], 1.0)], 500, seed=9,
                                          n_burnin=200, n_thinning=4))
+
+
+@pytest.mark.parametrize("m", [1, 2, 3, 4, 5, 6, 7, 8])
+def test_scan_limit_is_the_bound_the_scan_entries_check(m):
+    """evr_hvi_scan_limits (asked by acquisition._decompose before it takes the device box
+    decomposition) is the point-table bound of the scan entry points themselves: a keyed state
+    one row past it is refused by evr_hvi_forward_backward's host-side check with the LDS
+    message, before any launch.  For m = 2..5 the box decomposition's own limit lies beyond it
+    (n = 1485..1677 at m = 5), which is why both are asked."""
+    from everest_amd import _native, ops
+
+    lib = _native.load()
+    top = 65536 // (8 * m + 4)
+    assert ops.hvi_scan_supported(top, m) and not ops.hvi_scan_supported(top + 1, m)
+    assert not ops.hvi_scan_supported(0, m) and not ops.hvi_scan_supported(top, 9)
+    dummy = np.zeros(8, dtype=np.int64)
+    for stride, ok in ((top, True), (top + 1, False)):
+        st = _native.EvrQnehviState()
+        st.S, st.m, st.pts_stride = 1, m, stride
+        st.cell_off = st.cell_keys = st.cell_pts = st.cell_rank0 = dummy.ctypes.data
+        # work / G / dG stay NULL: an accepted state stops at the argument check that follows
+        rc = lib.evr_hvi_forward_backward(None, ctypes.byref(st), 1, None, None, None, None, None, None)
+        msg = lib.evr_last_error()
+        assert rc != 0 and ((b"bad arguments" in msg) if ok else (b"exceeds the LDS budget" in msg)), msg
+    box_top = max(n for n in range(1, 6000) if ops.box_device_supported(n, m))
+    assert (box_top + m > top) == (2 <= m <= 5)
+    if m == 5:
+        assert (top - m, box_top) == (1484, 1677)
