@@ -60,6 +60,17 @@ class EvrNei(ctypes.Structure):
     ]
 
 
+class EvrSobo(ctypes.Structure):
+    _fields_ = [
+        ("log", c_int), ("tau_relu", c_double), ("tau_max", c_double), ("best", c_void_p), ("best_stride", c_int),
+        ("n_term", c_int),
+        ("term_out", c_void_p), ("term_kind", c_void_p), ("term_w", c_void_p), ("term_p0", c_void_p),
+        ("term_p1", c_void_p), ("term_p2", c_void_p),
+        ("n_con", c_int),
+        ("con_out", c_void_p), ("con_sign", c_void_p), ("con_thr", c_void_p), ("con_eta", c_void_p),
+    ]
+
+
 _SIGS = {
     "evr_version": ([], c_int),
     "evr_last_error": ([], c_char_p),
@@ -171,6 +182,11 @@ _SIGS = {
                                     c_int], c_longlong),
     "evr_qnei_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
                        POINTER(EvrNei), c_int] + [c_void_p] * 5, c_int),
+    "evr_sobo_scan": ([c_void_p, c_int, c_int, c_int, c_int, POINTER(EvrSobo)] + [c_void_p] * 5, c_int),
+    "evr_qsobo_workspace_doubles": ([POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel), c_int,
+                                     c_int], c_longlong),
+    "evr_qsobo_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
+                        POINTER(EvrSobo), c_int] + [c_void_p] * 5, c_int),
     "evr_objective_general": ([c_void_p, c_int, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 4, c_int),
     "evr_objective_weights": ([c_void_p, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 3, c_int),
     "evr_cells_kd_limits": ([c_int, c_int, c_int, c_void_p], c_int),

@@ -1210,6 +1210,257 @@ class QLogEI(_NeiAcqf):
         return ops.sobol_normal(self.S, q, self.sampler_seed, self.dev)
 
 
+# ---------------------------------------------------------------------------------------
+# scalarised / output-constrained single-objective acquisitions over several model outputs
+# ---------------------------------------------------------------------------------------
+def _best_feasible(u: torch.Tensor, feas: torch.Tensor, fallback) -> torch.Tensor:
+    """[upstream] compute_best_feasible_objective on utilities u and hard feasibility feas
+    (... x n): max_k where(feas, u, iv) with iv = -inf when every leading entry has a feasible
+    row and ``fallback()`` (the mean - 6 sigma lower bound) otherwise."""
+    if bool(feas.any(-1).all()):
+        iv = torch.full((), -math.inf, dtype=u.dtype, device=u.device)
+    else:
+        iv = fallback()
+    return torch.where(feas, u, iv).amax(-1)
+
+
+def _lower_bound(spec: "ops.SoboSpec", mu: torch.Tensor, var: torch.Tensor) -> torch.Tensor:
+    """[upstream] _estimate_objective_lower_bound: min_k u(mu(x_k) - 6 sigma(x_k)); mu, var
+    m x n noise-free posterior moments in original units, sigma = sqrt(max(var, 0))."""
+    return spec.utility((mu - 6.0 * var.clamp_min(0.0).sqrt()).T).min()
+
+
+class _SoboAcqf(_NeiAcqf):
+    """Evaluation side of QSoboNEI / QSoboLogNEI / QSoboLogEI: the general chain over the m
+    model outputs with the scalarised, constraint-weighted scan of sobo_scan.hip between the
+    joint samples and their adjoint (evr_qsobo_eval) — [upstream]
+    SampleReducingMCAcquisitionFunction._apply_constraints weighs every (sample, point) before
+    the reduction over q, so the hypervolume chain's q-subset weighting does not apply.
+    Subclasses set gp, dev, S, M, nb, spec and the incumbent(s) ``best`` and call _finish_sobo.
+
+    BoTorch is not importable offline: the incumbent's mean - 6 sigma fallback and the constrained
+    prune are restated from memory of BoTorch and are parity-unpinned against it."""
+
+    @staticmethod
+    def _check_model(gp: GPBatch, spec: "ops.SoboSpec", name: str):
+        if gp.B != spec.m_model:
+            raise ValueError(f"{name}: the spec describes {spec.m_model} outputs, the model has {gp.B}")
+        if gp.mask is not None:
+            raise NotImplementedError(f"{name}: outputs fitted on different row sets are not supported")
+
+    def _finish_sobo(self, no_h: bool, log: bool, tau_relu: float, tau_max: float, X_pending_raw):
+        gp = self.gp
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        if log and not (tau_relu > 0 and tau_max > 0):
+            raise ValueError("tau_relu and tau_max must be positive")
+        self.m, self.n, self.nk = gp.B, gp.n, gp.n
+        self.log_acqf = bool(log)
+        self.tau_relu, self.tau_max = float(tau_relu), float(tau_max)
+        self.X_pending = None
+        if X_pending_raw is not None and np.asarray(X_pending_raw).shape[0] > 0:
+            self.X_pending = torch.as_tensor(np.asarray(X_pending_raw, dtype=np.float64).reshape(-1, gp.d), **f64)
+        self.n_pending = 0 if self.X_pending is None else int(self.X_pending.shape[0])
+        self.Xk = gp.Xn
+        self.Rr = gp.n + self.nb + (0 if no_h else self.S) + 1
+        self.state = ops.model_state(gp.n, self.nb, self.S, gp.const, gp.ym, gp.ys, gp.kxx, no_h=no_h, m=gp.B)
+        self._lo_c = gp.lo.to(torch.float64).contiguous()
+        self._scale_c = gp.inv_range.to(torch.float64).contiguous()
+        self.model = _native.EvrQnehviModel(n=gp.n, d=gp.d, kind=gp.kind, Xn=self.Xk.data_ptr(),
+                                            lengthscales=gp.ls.data_ptr(), shift=self._lo_c.data_ptr(),
+                                            scale=self._scale_c.data_ptr(), M=self.M.data_ptr())
+        self.best = self.best.to(**f64).reshape(-1).contiguous()
+        self.sb = self.spec.struct(log, tau_relu, tau_max, self.best)
+        self._zq_cache = {}
+        self._plans = {}
+        torch.cuda.synchronize(self.dev)
+
+    def _general(self, X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
+        """X: b x q x d -> (acq (b), dX b x q x d | None) through evr_qsobo_eval."""
+        b, q, d = X.shape
+        X = self._joint(X)
+        qq = X.shape[1]
+        g = _native.EvrQnGeneral()
+        g.q, g.zq = int(qq), self._zq(qq).data_ptr()
+        acq, dX = ops.qsobo_eval(self.state, g, self.model, self.sb, X.reshape(b * qq, d).contiguous(), backward,
+                                 gout)
+        if dX is not None:
+            dX = dX.view(b, qq, d)[:, :q].contiguous()
+        return acq, dX
+
+    def _torch_acq(self, q: int, fast: bool = False):
+        """The torch.classes.everest_amd.QsoboAcq behind torch.ops.everest_amd.qsobo_*."""
+        from . import torch_ops
+
+        torch_ops.load()
+        acq = self.__dict__.get("_torch_sobo")
+        if acq is None:
+            def raw(st):
+                return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8)
+            terms = torch.tensor(self.spec.terms, dtype=torch.float64).reshape(-1, 6)
+            cons = torch.tensor(self.spec.constraints, dtype=torch.float64).reshape(-1, 4)
+            acq = torch.classes.everest_amd.QsoboAcq(raw(self.state), raw(self.model), self.log_acqf, self.tau_relu,
+                                                     self.tau_max, self.best, terms, cons, self._device_tensors())
+            self._torch_sobo = acq
+        done = self.__dict__.setdefault("_torch_sobo_q", set())
+        if q not in done:
+            acq.set_samples(int(q), self._zq(q))
+            done.add(q)
+        return acq
+
+    def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        """X (b x q x d, or b x d for q = 1) -> acq (b), differentiable through the device
+        backward (torch.ops.everest_amd.qsobo_forward / qsobo_forward_backward)."""
+        from .torch_ops import QsoboFunction
+
+        X3 = self._joint(self._split(X)[0]).contiguous()
+        return QsoboFunction.apply(X3, self._torch_acq(X3.shape[1]))
+
+
+class QSoboNEI(_SoboAcqf):
+    """Device qNEI over m model outputs with a scalarised utility u(y) = sum_t w_t g_t(y[out_t])
+    and output constraints (``spec``: ops.SoboSpec) — what SoboStrategy builds when further
+    outputs carry constrained objectives, and AdditiveSoboStrategy always
+    (bofire/strategies/predictives/sobo.py:42-222):
+
+        acq = mean_s max_i [ (u(y_si) - best_s)_+ * exp(sum_c logsigmoid(-c(y_si) / eta_c)) ].
+
+    Construction follows QNEHVI per output (M = [L^-1; G; H^T; alpha^T], the baseline root and
+    draw, ops.model_state at m outputs) without cells.
+
+    Incumbent ([upstream] compute_best_feasible_objective): with feas = all c <= 0 (hard),
+    best_s = max_k where(feas_sk, u_sk, iv); iv = -inf when every sample has a feasible baseline
+    row, else min_k u(mu(x_k) - 6 sigma(x_k)) over the (pruned) baseline rows
+    (_estimate_objective_lower_bound).  Pruning ([upstream] prune_inferior_points with
+    constraints): infeasible draws take the same lower bound (over all baseline rows) before
+    the arg-max count.  Both are construction-time torch work on the device.
+
+    The +-6 sigma fallback and the constrained prune are written from memory of BoTorch (not
+    importable offline) and are parity-unpinned; the seed order follows QNEI (prune seed first)."""
+
+    _LOG = False
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, X_baseline_raw: np.ndarray, spec: "ops.SoboSpec",
+                 S: int = 512, sampler_seed: int = 0, prune_baseline: bool = True, prune_seed: int = 0,
+                 prune_samples: int = 2048, z_prune: Optional[torch.Tensor] = None,
+                 X_pending_raw: Optional[np.ndarray] = None, tau_relu: float = TAU_RELU,
+                 tau_max: float = TAU_MAX_SO):
+        self._check_model(gp, spec, type(self).__name__)
+        dev = gp.device
+        self.gp, self.dev, self.S, self.spec = gp, dev, int(S), spec
+        self.sampler_seed = int(sampler_seed)
+        n, S_, m = gp.n, self.S, gp.B
+        f64 = dict(dtype=torch.float64, device=dev)
+        first = {}
+        for i, row in enumerate(map(tuple, np.asarray(X_train_raw, dtype=np.float64))):
+            first.setdefault(row, i)
+        try:
+            base_rows = np.array([first[tuple(r)] for r in np.asarray(X_baseline_raw, dtype=np.float64)],
+                                 dtype=np.int64)
+        except KeyError as e:
+            raise ValueError("qNEI: every baseline point must be a training point of the model") from e
+        if base_rows.shape[0] == 0:
+            raise ValueError("qNEI needs a non-empty baseline")
+        # joint posterior per output at the training inputs, shared by prune and baseline
+        K = gp.kernel_train(noise=False)                                    # m x n x n
+        mu_t = ops.gemm(K, gp.alpha.unsqueeze(-1))[..., 0]
+        mu_train = gp.ym[:, None] + gp.ys[:, None] * (gp.const[:, None] + mu_t)
+        A = ops.gemm(gp.Linv, K)                                            # L^-1 K
+        Sig = ops.gemm(A, A, transA=True, alpha=-1.0, beta=1.0, out=K)      # K - A^T A (in place)
+        ys2 = (gp.ys ** 2).contiguous()
+        ops.scale_batched(Sig, ys2)
+        var_train = torch.diagonal(Sig, dim1=-2, dim2=-1)                   # m x n
+
+        def draws(L, Z, rows):
+            """m x k x S' root times base samples -> S' x k x m model outputs."""
+            return (mu_train[:, rows, None] + ops.gemm(L, Z)).permute(2, 1, 0)
+
+        self.prune_counts = None
+        if prune_baseline:
+            cand = torch.as_tensor(base_rows, device=dev)
+            nc = int(cand.shape[0])
+            Lp, _, _ = ops.cholesky(Sig[:, cand][:, :, cand].contiguous(), 1e-8, 3)
+            if z_prune is None:
+                Zp = sobol_base_samples(prune_samples, nc, m, prune_seed, dev)          # m x nc x S'
+            else:
+                Zp = z_prune.to(**f64).reshape(-1, nc, m).permute(2, 1, 0).contiguous()
+            Yp = draws(Lp, Zp, cand)
+            up, fp = spec.utility(Yp), spec.feasible(Yp)
+            if not bool(fp.all()):
+                up = torch.where(fp, up, _lower_bound(spec, mu_train[:, cand], var_train[:, cand]))
+            counts = torch.bincount(up.argmax(dim=1), minlength=nc)
+            self.prune_counts = counts.cpu().numpy()
+            base_rows = base_rows[np.nonzero(self.prune_counts)[0]]
+        nb = int(base_rows.shape[0])
+        self.nb, self.base_rows = nb, base_rows
+        idx = torch.as_tensor(base_rows, device=dev)
+        # baseline root, draw and per-sample incumbent
+        self.L_base, self.base_jitter, _ = ops.cholesky(Sig[:, idx][:, :, idx].contiguous(), 1e-8, 3)
+        Zb = sobol_base_samples(S_, nb, m, sampler_seed, dev)                           # m x nb x S
+        self._Zb = Zb
+        Yb = draws(self.L_base, Zb, idx)                                                # S x nb x m
+        self.best = _best_feasible(spec.utility(Yb), spec.feasible(Yb),
+                                   lambda: _lower_bound(spec, mu_train[:, idx], var_train[:, idx]))
+        # operator M = [L^-1; G; H^T; alpha^T] per output, G = s^2 L_base^-1 (P - A_b^T L^-1), H = G^T Z_base
+        Rr = n + nb + S_ + 1
+        M = torch.empty(m, Rr, n, **f64)
+        M[:, :n].copy_(gp.Linv)
+        E = ops.gemm(A[:, :, idx].contiguous(), gp.Linv, transA=True, alpha=-1.0)
+        ops.add_selection(E, idx.to(torch.int32), None)
+        ops.scale_batched(E, ys2)
+        ops.trsm(self.L_base, E)
+        M[:, n:n + nb].copy_(E)
+        ops.gemm_into(M[:, n + nb:n + nb + S_], Zb, E, transA=True)
+        M[:, Rr - 1].copy_(gp.alpha)
+        self.M = M
+        self._finish_sobo(False, self._LOG, tau_relu, tau_max, X_pending_raw)
+
+    def z_base_host(self) -> torch.Tensor:
+        """The baseline base samples (S x nb x m, host), the oracle's layout."""
+        return self._Zb.permute(2, 1, 0).cpu().contiguous()
+
+    def _draw_zq(self, q: int) -> torch.Tensor:
+        """Rows nb .. nb+q-1 of the (nb+q)*m-dimensional draw of the sampler seed."""
+        nb, m = self.nb, self.m
+        return ops.sobol_normal(self.S, (nb + q) * m, self.sampler_seed, self.dev, d0=nb * m, nd=q * m)
+
+
+class QSoboLogNEI(QSoboNEI):
+    """Device qLogNEI (fat = True) over m model outputs — the QSoboNEI construction with the log
+    scan acq = logmeanexp_s fatmax_i [ log fatplus(u(y_si) - best_s; tau_relu)
+    + sum_c log_fatmoid(-c(y_si) / eta_c) ; tau_max ].  Parity-unpinned like QSoboNEI."""
+
+    _LOG = True
+
+
+class QSoboLogEI(_SoboAcqf):
+    """Device qLogEI (``log=False``: qEI) over m model outputs with the utility and constraints of
+    ``spec``: plain joint samples per output (M = [L^-1; alpha^T], the S x (q + n_pending) x m
+    Sobol-normal draw of the sampler seed) and the scalar incumbent best_f — the rule of
+    QSoboNEI's incumbent applied to the posterior means at X_train.  Parity-unpinned like
+    QSoboNEI (the mean - 6 sigma fallback is restated from memory of BoTorch)."""
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, spec: "ops.SoboSpec", S: int = 512, seed: int = 0,
+                 X_pending_raw: Optional[np.ndarray] = None, tau_relu: float = TAU_RELU,
+                 tau_max: float = TAU_MAX_SO, log: bool = True):
+        self._check_model(gp, spec, "QSoboLogEI")
+        self.gp, self.dev, self.S, self.nb, self.spec = gp, gp.device, int(S), 0, spec
+        self.sampler_seed = int(seed)
+        Xt = torch.as_tensor(np.asarray(X_train_raw, dtype=np.float64), device=self.dev)
+        mean, var = gp.posterior(Xt)                                        # m x n each
+        self.best = _best_feasible(spec.utility(mean.T), spec.feasible(mean.T),
+                                   lambda: _lower_bound(spec, mean, var)).reshape(1)
+        self.best_f = float(self.best.item())
+        self.M = gp.M
+        self._finish_sobo(True, log, tau_relu, tau_max, X_pending_raw)
+
+    def z_base_host(self) -> None:
+        """No baseline draw (plain joint sampling)."""
+        return None
+
+    def _draw_zq(self, q: int) -> torch.Tensor:
+        return ops.sobol_normal(self.S, q * self.m, self.sampler_seed, self.dev)
+
+
 class QEI:
     """Device qEI (q = 1, one output) — [upstream] qExpectedImprovement as built by
     ``get_acquisition_function("qEI", ...)`` from SoboStrategy._get_acqfs

@@ -27,6 +27,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "qg_obj.hpp"
 #include "../../include/everest_amd.h"
 
 namespace evr {
@@ -47,61 +48,9 @@ long long hvi_raw_workspace(const evr_qnehvi_state* st, int b, bool backward);
 int hvi_raw(hipStream_t s, const evr_qnehvi_state* st, int b, const double* G, bool backward, double* work,
             double* dG, int* nsplit);
 
-constexpr int QG_MAXM = 8, QG_MAXC = 16;
-
-// objectives / constraints by value (kernel argument)
-struct QgObj {
-  int m, mo, nc;
-  int oo[QG_MAXM], ok[QG_MAXM];
-  double p0[QG_MAXM], p1[QG_MAXM];
-  int co[QG_MAXC];
-  double cs[QG_MAXC], ct[QG_MAXC], ce[QG_MAXC];
-};
-
 struct QgDims {
   int n, nb, nh, S, m, b;
 };
-
-__device__ __forceinline__ double qg_obj(const QgObj& o, int k, double y) {
-  if (o.ok[k] == EVR_OBJ_AFFINE) return fma(o.p0[k], y, o.p1[k]);
-  return -pow(fabs(y - o.p0[k]), o.p1[k]);   // CloseToTarget: -|y - t|^e
-}
-
-__device__ __forceinline__ double qg_dobj(const QgObj& o, int k, double y) {
-  if (o.ok[k] == EVR_OBJ_AFFINE) return o.p0[k];
-  const double u = y - o.p0[k], e = o.p1[k];
-  if (u == 0.0) return 0.0;                  // torch: sign(0) = 0 in abs' backward
-  return -e * pow(fabs(u), e - 1.0) * (u > 0.0 ? 1.0 : -1.0);
-}
-
-// log-sigmoid, stable: min(x, 0) - log1p(exp(-|x|))
-__device__ __forceinline__ double qg_logsig(double x) { return fmin(x, 0.0) - log1p(exp(-fabs(x))); }
-__device__ __forceinline__ double qg_sig(double x) {
-  return x >= 0.0 ? 1.0 / (1.0 + exp(-x)) : exp(x) / (1.0 + exp(x));
-}
-
-// [upstream] botorch.utils.safe_math.log_fatmoid — the fat-tailed (Cauchy, O(1/x^2) for
-// x -> -inf) smooth Heaviside that compute_smoothed_feasibility_indicator(log=True, fat=True)
-// uses in qLogNEHVI / qLogEHVI:  fatmoid(x) = 2/3 cauchy(x - m) for x < 0,
-// 1 - 2/3 cauchy(x + m) otherwise, cauchy(x) = 1 / (1 + x^2), m = sqrt(1/3) (continuous, = 1/2
-// at 0).  Log evaluated without cancellation on both branches; qg_dlog_fatmoid is its slope.
-constexpr double QG_FATMOID_M = 0.57735026918962576;
-__device__ __forceinline__ double qg_log_fatmoid(double x) {
-  if (x < 0.0) {
-    const double u = x - QG_FATMOID_M;
-    return -0.40546510810816438 - log1p(u * u);   // log(2/3) - log(1 + u^2)
-  }
-  const double u = x + QG_FATMOID_M;
-  return log1p(-(2.0 / 3.0) / (1.0 + u * u));
-}
-__device__ __forceinline__ double qg_dlog_fatmoid(double x) {
-  if (x < 0.0) {
-    const double u = x - QG_FATMOID_M;
-    return -2.0 * u / (1.0 + u * u);
-  }
-  const double u = x + QG_FATMOID_M, w = 1.0 + u * u, c = (2.0 / 3.0) / w;
-  return 2.0 * u * c / (w * (1.0 - c));
-}
 
 // fixed-order block sum over 256 threads (4 waves): xor-butterfly in the wave, then waves 0..3
 __device__ __forceinline__ double qg_block_sum(double v, double* red4) {
@@ -1270,14 +1219,17 @@ namespace evr {
 int nei_scan_launch(hipStream_t s, int q, bool log_mode, int S, int b, const double* Y, const double* best,
                     int best_stride, double oa, double ob, double tr, double tm, const int* flags,
                     const double* gout, double* acq, double* dY);
+int sobo_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_sobo* sb, const double* Y,
+                     const int* flags, const double* gout, double* acq, double* dY);
 
 struct QnLayout {
   size_t Kx, R, P, Wf, Y, Lq, flags, dY, cf, dKqq, cm, gR, dKx, Wb, kg, total;
 };
 
+// m = stm->m model outputs (1 for evr_qnei_eval)
 static QnLayout qn_layout(const evr_qnehvi_state* stm, int q, int d, int b, bool backward) {
   QnLayout L{};
-  const size_t n = stm->n, S = stm->S, bq = (size_t)b * q;
+  const size_t m = stm->m, n = stm->n, S = stm->S, bq = (size_t)b * q;
   const size_t Rr = (size_t)qn_rows(stm);
   size_t o = 0;
   auto take = [&](size_t doubles) {
@@ -1285,21 +1237,21 @@ static QnLayout qn_layout(const evr_qnehvi_state* stm, int q, int d, int b, bool
     o += (doubles + 31) & ~(size_t)31;
     return r;
   };
-  L.Kx = take(n * bq);
-  L.R = take(Rr * bq);
-  L.P = take((size_t)evr_qnehvi_norms_rows(stm) * 2 * bq);
+  L.Kx = take(m * n * bq);
+  L.R = take(m * Rr * bq);
+  L.P = take(m * (size_t)evr_qnehvi_norms_rows(stm) * 2 * bq);
   L.Wf = take(proj_forward_ws_doubles(stm, (int)bq));
-  L.Y = take(S * bq);
-  L.Lq = take((size_t)b * q * q);
-  L.flags = take(((size_t)b + 1) / 2);
+  L.Y = take(S * m * bq);
+  L.Lq = take(m * b * q * q);
+  L.flags = take((m * b + 1) / 2);
   if (backward) {
-    L.dY = take(S * bq);
-    L.cf = take((size_t)b * q * q);
-    L.dKqq = take((size_t)b * q * q);
-    L.cm = take(bq);
-    L.gR = take(Rr * bq);
-    L.dKx = take(n * bq);
-    L.Wb = take(dg_gemm_ws_doubles(true, (int)n, (int)bq, (int)Rr, 1));
+    L.dY = take(S * m * bq);
+    L.cf = take(m * b * q * q);
+    L.dKqq = take(m * b * q * q);
+    L.cm = take(m * bq);
+    L.gR = take(m * Rr * bq);
+    L.dKx = take(m * n * bq);
+    L.Wb = take(dg_gemm_ws_doubles(true, (int)n, (int)bq, (int)Rr, (int)m));
     L.kg = take(kcross_grad_ws_doubles((int)n, (int)bq, d));
   }
   L.total = o;
@@ -1387,5 +1339,78 @@ int evr_qnei_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_genera
   return 0;
 }
 
-}  // extern "C"
+// qSobo*: the same chain over m model outputs with the scalarised, constraint-weighted scan of
+// sobo_scan.hip (SoboStrategy with constrained objectives, AdditiveSoboStrategy).
+long long evr_qsobo_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                      const evr_qnehvi_model* md, int b, int backward) {
+  if (!stm || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q || stm->m < 1 || stm->m > QG_MAXM) return 0;
+  return (long long)qn_layout(stm, g->q, md->d, b, backward != 0).total;
+}
 
+int evr_qsobo_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                   const evr_sobo* sb, int b, const double* X, const double* gout, double* work, double* acq,
+                   double* dX) {
+  EVR_CHECK(stm && g && md && sb, "evr_qsobo_eval: null argument");
+  EVR_CHECK(g->q >= 1 && g->q <= EVR_QNG_MAX_Q, "evr_qsobo_eval: q = %d outside 1..%d", g->q, EVR_QNG_MAX_Q);
+  EVR_CHECK(stm->m >= 1 && stm->m <= QG_MAXM, "evr_qsobo_eval: %d model outputs outside 1..%d", stm->m, QG_MAXM);
+  EVR_CHECK(md->n == stm->n && md->d >= 1 && md->M && md->Xn && md->lengthscales && g->zq && stm->c && stm->ym &&
+                stm->ys && stm->kxx && stm->S >= 1,
+            "evr_qsobo_eval: inconsistent model / state");
+  EVR_CHECK(X && work && acq && b >= 0, "evr_qsobo_eval: bad arguments");
+  if (b == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const int q = g->q, m = stm->m, n = stm->n, d = md->d, S = stm->S;
+  const int bq = b * q;
+  const bool backward = dX != nullptr;
+  const QnLayout L = qn_layout(stm, q, d, b, backward);
+  double* w = work;
+  double* Kx = w + L.Kx;
+  double* R = w + L.R;
+  double* Y = w + L.Y;
+  double* Lq = w + L.Lq;
+  int* flags = (int*)(w + L.flags);
+  double* dY = backward ? w + L.dY : nullptr;
+  const QgDims dm{n, stm->nb, qn_nh(stm), S, m, b};
+  if (int rc = evr_kernel_matrix(s, md->kind, m, n, bq, d, md->Xn, nullptr, nullptr, X, md->shift, md->scale,
+                                 md->lengthscales, nullptr, nullptr, Kx))
+    return rc;
+  if (int rc = proj_forward(s, stm, bq, md->M, Kx, R, w + L.P, L.Wf != L.Y ? w + L.Wf : nullptr)) return rc;
+#define GO(QQ)                                                                                                   \
+  qg_gram_samples<QQ><<<dim3(b, m), 256, 0, s>>>(dm, md->kind, d, R, X, md->lengthscales, md->shift, md->scale,   \
+                                                 stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags);       \
+  EVR_LAUNCH_CHECK()
+  QG_SWITCH(q, GO);
+#undef GO
+  if (int rc = sobo_scan_launch(s, q, m, S, b, sb, Y, flags, gout, acq, dY)) return rc;
+  if (!backward) return 0;
+  double* cf = w + L.cf;
+  double* dKqq = w + L.dKqq;
+  double* cm = w + L.cm;
+  double* gR = w + L.gR;
+  double* dKx = w + L.dKx;
+  const int Rr = qn_rows(stm);
+#define GO(QQ)                                                                                                   \
+  qg_samples_bwd<QQ><<<dim3(b, m), 256, 0, s>>>(dm, dY, g->zq, Lq, stm->ys, cf, dKqq, cm);                        \
+  EVR_LAUNCH_CHECK();                                                                                            \
+  qg_gen_gr<QQ><<<dim3(m * Rr, cdiv(bq, 256)), 256, 0, s>>>(dm, R, dY, cf, cm, stm->ys, gR);                      \
+  EVR_LAUNCH_CHECK()
+  QG_SWITCH(q, GO);
+#undef GO
+  if (int rc = dg_gemm(s, true, n, bq, Rr, 1.0, md->M, n, (long long)Rr * n, gR, bq, (long long)Rr * bq, 0.0, dKx, bq,
+                       (long long)n * bq, m, w + L.Wb))
+    return rc;
+  if (int rc = kcross_grad_launch(s, md->kind, m, n, bq, d, md->Xn, nullptr, nullptr, X, md->shift, md->scale,
+                                  md->lengthscales, nullptr, dKx, dX, w + L.kg))
+    return rc;
+  if (q > 1) {
+#define GO(QQ)                                                                                                   \
+  qg_kqq_grad<QQ><<<cdiv(bq, 64), 64, 0, s>>>(b, m, d, md->kind, X, md->lengthscales, md->shift, md->scale,       \
+                                              stm->kxx, dKqq, dX);                                               \
+  EVR_LAUNCH_CHECK()
+    QG_SWITCH(q, GO);
+#undef GO
+  }
+  return 0;
+}
+
+}  // extern "C"

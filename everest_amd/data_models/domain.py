@@ -550,6 +550,12 @@ class Outputs(_Features):
         keep &= ~experiments[list(keys)].isna().to_numpy().any(axis=1)
         return experiments if keep.all() else experiments[keep]
 
+    def preprocess_experiments_one_valid_output(self, output_feature_key: str,
+                                                experiments: pd.DataFrame) -> pd.DataFrame:
+        """The rows with a valid, non-NaN observation of one output (what the adaptive
+        objectives see as x_adapt)."""
+        return self.preprocess_experiments_all_valid_outputs(experiments, [output_feature_key])
+
     def validate_experiments(self, experiments: pd.DataFrame) -> pd.DataFrame:
         for feat in self.features:
             if feat.key not in experiments:

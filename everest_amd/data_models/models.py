@@ -16,8 +16,8 @@ from typing import Annotated, Dict, List, Literal, Optional, Union
 
 from pydantic import Field, PositiveInt, field_validator, model_validator
 
-from .domain import (BaseModel, CategoricalInput, CloseToTargetObjective, ContinuousOutput, Domain, Inputs,
-                     MaximizeObjective, MinimizeObjective, Outputs)
+from .domain import (BaseModel, CategoricalInput, CloseToTargetObjective, ConstrainedObjective, ContinuousOutput,
+                     Domain, Inputs, MaximizeObjective, MinimizeObjective, Objective, Outputs)
 
 
 class CategoricalEncodingEnum(str, Enum):
@@ -388,9 +388,41 @@ class MoboStrategy(MultiobjectiveStrategy):
 
 
 class SoboStrategy(BotorchStrategy):
+    """bofire/data_models/strategies/predictives/sobo.py:15-62."""
     type: Literal["SoboStrategy"] = "SoboStrategy"
     acquisition_function: AnySingleObjectiveAcquisitionFunction = Field(default_factory=qLogNEI)
 
+    @field_validator("domain")
+    @classmethod
+    def validate_is_singleobjective(cls, v):
+        """sobo.py:50-62: at most one objective that is not a ConstrainedObjective (the
+        reference subtracts the outputs without an objective from that count)."""
+        if len(v.outputs) == 1:
+            return v
+        free = len(v.outputs.get_by_objective(excludes=ConstrainedObjective))
+        none = sum(1 for f in v.outputs.get().features if getattr(f, "objective", None) is None)
+        if free - none > 1:
+            raise ValueError("SOBO strategy can only deal with one no-constraint objective.")
+        return v
 
-AnyStrategy = Annotated[Union[QnehviStrategy, QehviStrategy, MoboStrategy, SoboStrategy, RandomStrategy],
-                       Field(discriminator="type")]
+
+class AdditiveSoboStrategy(BotorchStrategy):
+    """bofire/data_models/strategies/predictives/sobo.py:65-75: the weighted sum of the
+    objectives; ``use_output_constraints`` keeps the constrained objectives as separate output
+    constraints (True) or absorbs them into the sum (False)."""
+    type: Literal["AdditiveSoboStrategy"] = "AdditiveSoboStrategy"
+    acquisition_function: AnySingleObjectiveAcquisitionFunction = Field(default_factory=qLogNEI)
+    use_output_constraints: bool = True
+
+    @field_validator("domain")
+    @classmethod
+    def validate_is_multiobjective(cls, v):
+        if len(v.outputs.get_by_objective(Objective)) < 2:
+            raise ValueError("Additive SOBO strategy requires at least 2 outputs with objectives. Consider SOBO "
+                             "strategy instead.")
+        return v
+
+
+AnyStrategy = Annotated[Union[QnehviStrategy, QehviStrategy, MoboStrategy, SoboStrategy, AdditiveSoboStrategy,
+                              RandomStrategy],
+                        Field(discriminator="type")]

@@ -511,11 +511,12 @@ def qlog_eval(stm: EvrQnehviState, sth: EvrQnehviState, g: EvrQnGeneral, model: 
     return acq, dX
 
 
-def model_state(n, nb, S, c, ym, ys, kxx, no_h: bool = False) -> EvrQnehviState:
-    """Model-side state of a single-output chain without cells (evr_qnei_eval): the operator
-    layout (n, nb, S, no_h) and the output's constant / standardisation / prior variance."""
+def model_state(n, nb, S, c, ym, ys, kxx, no_h: bool = False, m: int = 1) -> EvrQnehviState:
+    """Model-side state of a chain without cells (evr_qnei_eval: m = 1; evr_qsobo_eval: m model
+    outputs): the operator layout (n, nb, S, no_h) and the per-output constant / standardisation
+    / prior variance."""
     st = EvrQnehviState()
-    st.n, st.nb, st.S, st.m = int(n), int(nb), int(S), 1
+    st.n, st.nb, st.S, st.m = int(n), int(nb), int(S), int(m)
     st.no_h = int(bool(no_h))
     st.c, st.ym, st.ys, st.kxx = c.data_ptr(), ym.data_ptr(), ys.data_ptr(), kxx.data_ptr()
     return st
@@ -571,6 +572,126 @@ def qnei_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviMod
     acq = torch.empty(b, dtype=torch.float64, device=X.device)
     dX = torch.empty_like(X) if backward else None
     call("evr_qnei_eval", _stream(), ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), ctypes.byref(nei), b,
+         X.data_ptr(), _p(None if gout is None else _dev(gout, "gout")), work.data_ptr(), acq.data_ptr(), _p(dX))
+    return acq, dX
+
+
+OBJ_SIGMOID, OBJ_TARGET = 2, 3
+
+
+class SoboSpec:
+    """Scalarised utility over model outputs with output constraints for the single-objective
+    scan (sobo_scan.hip, evr_sobo): u(y) = sum_t w_t g_t(y[out_t]).
+
+    terms: [(output, kind, w, p0, p1, p2)] — OBJ_AFFINE p0*y + p1, OBJ_CLOSE_TO_TARGET
+    -|y - p0|^p1, OBJ_SIGMOID 1/(1+exp(-p0*(y-p1))) (p0 = +steepness MaximizeSigmoid,
+    -steepness MinimizeSigmoid), OBJ_TARGET sig(p0*(y-(p1-p2))) * (1 - sig(p0*(y-(p1+p2))))
+    (bofire/utils/torch_tools.py:384-450).  constraints: [(output, sign, threshold, eta)] as in
+    ``GeneralSpec``."""
+
+    def __init__(self, m_model: int, terms, constraints=()):
+        self.m_model = int(m_model)
+        self.terms = [(int(o), int(k), float(w), float(a), float(b), float(c)) for o, k, w, a, b, c in terms]
+        self.constraints = [(int(o), float(sg), float(t), float(e)) for o, sg, t, e in constraints]
+        if not 1 <= len(self.terms) <= 8 or len(self.constraints) > 16:
+            raise ValueError("sobo scan: 1..8 terms and at most 16 output constraints")
+        for o, *_ in self.terms + self.constraints:
+            if not 0 <= o < self.m_model:
+                raise ValueError(f"sobo scan: output index {o} outside the model's {self.m_model} outputs")
+        for _, k, *_ in self.terms:
+            if k not in (OBJ_AFFINE, OBJ_CLOSE_TO_TARGET, OBJ_SIGMOID, OBJ_TARGET):
+                raise ValueError(f"sobo scan: term kind {k}")
+        tm = self.terms
+        self._tarrs = (np.array([t[0] for t in tm], np.int32), np.array([t[1] for t in tm], np.int32)) + tuple(
+            np.array([t[i] for t in tm], np.float64) for i in (2, 3, 4, 5))
+        cs = self.constraints or [(0, 0.0, 0.0, 1.0)]
+        self._carrs = (np.array([c[0] for c in cs], np.int32), np.array([c[1] for c in cs], np.float64),
+                       np.array([c[2] for c in cs], np.float64), np.array([c[3] for c in cs], np.float64))
+
+    def struct(self, log: bool, tau_relu: float, tau_max: float, best: torch.Tensor) -> "_native.EvrSobo":
+        """evr_sobo over ``best`` (device; S per-sample incumbents, or one value: stride 0).  The
+        struct points into this spec's host arrays and into ``best``: keep both alive."""
+        best = _dev(best, "best")
+        sb = _native.EvrSobo()
+        sb.log, sb.tau_relu, sb.tau_max = int(bool(log)), float(tau_relu), float(tau_max)
+        sb.best, sb.best_stride = best.data_ptr(), 0 if best.numel() == 1 else 1
+        sb.n_term, sb.n_con = len(self.terms), len(self.constraints)
+        (sb.term_out, sb.term_kind, sb.term_w, sb.term_p0, sb.term_p1,
+         sb.term_p2) = (a.ctypes.data for a in self._tarrs)
+        sb.con_out, sb.con_sign, sb.con_thr, sb.con_eta = (a.ctypes.data for a in self._carrs)
+        return sb
+
+    @staticmethod
+    def _term(k: int, a: float, b: float, c: float, y):
+        xp = torch if isinstance(y, torch.Tensor) else np
+        if k == OBJ_AFFINE:
+            return a * y + b
+        if k == OBJ_CLOSE_TO_TARGET:
+            return -xp.abs(y - a) ** b
+        if k == OBJ_SIGMOID:
+            return 1.0 / (1.0 + xp.exp(-a * (y - b)))
+        return 1.0 / (1.0 + xp.exp(-a * (y - (b - c)))) * (1.0 - 1.0 / (1.0 + xp.exp(-a * (y - (b + c)))))
+
+    def utility(self, Y):
+        """u of model-output rows Y (... x m_model; numpy array or torch tensor)."""
+        u = 0.0
+        for o, k, w, a, b, c in self.terms:
+            u = u + w * self._term(k, a, b, c, Y[..., o])
+        return u
+
+    def feasible(self, Y):
+        """Hard feasibility (every c <= 0) of model-output rows Y (... x m_model)."""
+        xp = torch if isinstance(Y, torch.Tensor) else np
+        ok = xp.ones_like(Y[..., 0]) > 0
+        for o, sg, t, _ in self.constraints:
+            ok = ok & (sg * (Y[..., o] - t) <= 0)
+        return ok
+
+
+def sobo_scan(Y: torch.Tensor, q: int, best: torch.Tensor, spec: SoboSpec, log: bool = False,
+              tau_relu: float = 1e-6, tau_max: float = 1e-2, flags: Optional[torch.Tensor] = None,
+              gout: Optional[torch.Tensor] = None, backward: bool = False):
+    """Scalarised, constraint-weighted scan alone (evr_sobo_scan): Y S x m_model x (b*q) joint
+    samples (point i of candidate c at column c*q + i), best S incumbents or one ->
+    (acq (b), dY like Y | None).  flags: m_model x b."""
+    Y, best = _dev(Y, "Y"), _dev(best, "best")
+    S, m, bq = Y.shape
+    q = int(q)
+    if m != spec.m_model:
+        raise ValueError(f"Y has {m} outputs, the spec {spec.m_model}")
+    if q < 1 or bq % q:
+        raise ValueError(f"{bq} columns are not a multiple of q = {q}")
+    if best.numel() not in (1, S):
+        raise ValueError(f"best needs 1 or S = {S} values, got {best.numel()}")
+    b = bq // q
+    flags = None if flags is None else _dev(flags, "flags", torch.int32)
+    gout = None if gout is None else _dev(gout, "gout")
+    if (flags is not None and flags.numel() != m * b) or (gout is not None and gout.numel() != b):
+        raise ValueError("flags need one entry per (output, candidate), gout one per candidate")
+    acq = torch.empty(b, dtype=torch.float64, device=Y.device)
+    dY = torch.empty_like(Y) if backward else None
+    sb = spec.struct(log, tau_relu, tau_max, best)
+    call("evr_sobo_scan", _stream(), q, m, S, b, ctypes.byref(sb), Y.data_ptr(), _p(flags), _p(gout),
+         acq.data_ptr(), _p(dY))
+    return acq, dY
+
+
+def qsobo_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviModel", sb: "_native.EvrSobo",
+               X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
+    """Constrained / scalarised qNEI, qLogNEI, qLogEI, qEI over m model outputs (evr_qsobo_eval):
+    X (b*q) x d raw candidates -> acq (b) [, dX (b*q) x d]."""
+    X = _dev(X, "X")
+    q = int(g.q)
+    bq, d = X.shape
+    if bq % q:
+        raise ValueError(f"{bq} rows are not a multiple of q = {q}")
+    b = bq // q
+    lib = _native.load()
+    work = _workspace(lib.evr_qsobo_workspace_doubles(ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), b,
+                                                      int(backward)), X.device)
+    acq = torch.empty(b, dtype=torch.float64, device=X.device)
+    dX = torch.empty_like(X) if backward else None
+    call("evr_qsobo_eval", _stream(), ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), ctypes.byref(sb), b,
          X.data_ptr(), _p(None if gout is None else _dev(gout, "gout")), work.data_ptr(), acq.data_ptr(), _p(dX))
     return acq, dX
 

@@ -20,8 +20,8 @@ import torch
 
 from . import data_models as dm
 from . import ops
-from .acquisition import (QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI,
-                          prefetch_scramble)
+from .acquisition import (QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI, QSoboLogEI,
+                          QSoboLogNEI, QSoboNEI, prefetch_scramble)
 from .data_models.domain import CloseToTargetObjective, MaximizeObjective, MinimizeObjective
 from .optim import (OptimizeStats, hit_and_run, host_values, optimize_acqf, optimize_acqf_mixed,
                     prefetch_raw_samples)
@@ -728,37 +728,115 @@ class MoboStrategy(_MultiobjectiveMixin, BotorchStrategy):
         return [acqf]
 
 
+def sobo_term(objective, idx: int, w: float = 1.0, x_adapt=None):
+    """get_objective_callable (bofire/utils/torch_tools.py:384-450) as a term of the scalarised
+    scan (output, kind, w, p0, p1, p2): Maximize / Minimize / CloseToTarget as ``objective_term``,
+    MaximizeSigmoid / MovingMaximizeSigmoid -> sigmoid with p0 = +steepness, MinimizeSigmoid ->
+    p0 = -steepness (1 - sig(x) = sig(-x)), Target -> (steepness, target, tolerance)."""
+    if isinstance(objective, dm.MovingMaximizeSigmoidObjective):
+        if x_adapt is None:
+            raise ValueError("MovingMaximizeSigmoidObjective needs x_adapt (the observed values)")
+        return (int(idx), ops.OBJ_SIGMOID, float(w), float(objective.steepness),
+                float(np.asarray(x_adapt).max()) + objective.tp, 0.0)
+    if isinstance(objective, dm.MaximizeSigmoidObjective):
+        return (int(idx), ops.OBJ_SIGMOID, float(w), float(objective.steepness), float(objective.tp), 0.0)
+    if isinstance(objective, dm.MinimizeSigmoidObjective):
+        return (int(idx), ops.OBJ_SIGMOID, float(w), -float(objective.steepness), float(objective.tp), 0.0)
+    if isinstance(objective, dm.TargetObjective):
+        return (int(idx), ops.OBJ_TARGET, float(w), float(objective.steepness), float(objective.target_value),
+                float(objective.tolerance))
+    o, k, p0, p1 = objective_term(objective, idx)
+    return (o, k, float(w), p0, p1, 0.0)
+
+
+def sobo_objective_spec(outputs, output_keys: Sequence[str], experiments: Optional[pd.DataFrame] = None,
+                        additive: bool = False, use_output_constraints: bool = True):
+    """(terms, constraints) of the single-objective family over the model outputs ``output_keys``
+    (host only, no device):
+
+    SoboStrategy._get_objective_and_constraints (bofire/strategies/predictives/sobo.py:92-152):
+    one term of weight 1 — the first output whose objective is not a ConstrainedObjective, else
+    the first objective's own callable (a sigmoid / target term).
+    AdditiveSoboStrategy (sobo.py:164-222, get_additive_botorch_objective): u = sum w * g over the
+    non-constraint objectives (``use_output_constraints``) or over every objective (not).
+    Constraints (get_output_constraints) only when at least one ConstrainedObjective exists AND
+    more than one objective exists (and, additive, ``use_output_constraints``)."""
+    keys = list(output_keys)
+    feats = outputs.get_by_objective(dm.domain.Objective).features
+
+    def x_adapt(f):
+        if not isinstance(f.objective, dm.MovingMaximizeSigmoidObjective):
+            return None
+        if experiments is None:
+            raise ValueError("MovingMaximizeSigmoidObjective needs the experiments")
+        return outputs.preprocess_experiments_one_valid_output(f.key, experiments)[f.key].values
+
+    constrained = [f for f in feats if isinstance(f.objective, dm.ConstrainedObjective)]
+    free = [f for f in feats if not isinstance(f.objective, dm.ConstrainedObjective)]
+    if not feats:
+        raise ValueError("no output carries an objective")
+    if additive:
+        chosen = free if use_output_constraints else feats
+        if not chosen:
+            raise ValueError("AdditiveSoboStrategy(use_output_constraints=True) needs an objective that is not "
+                             "a constrained objective")
+        terms = [sobo_term(f.objective, keys.index(f.key), f.objective.w, x_adapt(f)) for f in chosen]
+    else:
+        f = free[0] if free else feats[0]
+        terms = [sobo_term(f.objective, keys.index(f.key), 1.0, x_adapt(f))]
+    constraints = []
+    if constrained and len(feats) > 1 and (use_output_constraints or not additive):
+        constraints = get_output_constraints(outputs, experiments, keys)
+    return terms, constraints
+
+
 class SoboStrategy(BotorchStrategy):
-    """bofire/strategies/predictives/sobo.py:40-120 — qLogNEI (the data model's default),
-    qNEI, qLogEI and qEI on the device; single output, no output constraints."""
+    """bofire/strategies/predictives/sobo.py:40-152 — qLogNEI (the data model's default), qNEI,
+    qLogEI and qEI on the device.  One affine objective on a single-output model without output
+    constraints runs QLogNEI / QNEI / QLogEI / QEI / QEIJoint (nei_scan.hip); every other
+    shape — further outputs with MaximizeSigmoid / MinimizeSigmoid / Target objectives as output
+    constraints, a sigmoid / target / close-to-target objective of its own — runs QSoboLogNEI /
+    QSoboNEI / QSoboLogEI over all model outputs (sobo_scan.hip)."""
+
+    _additive = False
 
     def __init__(self, data_model, dist=None, **kwargs):
         super().__init__(data_model, dist=dist)
         self.acquisition_function = data_model.acquisition_function
+        self.use_output_constraints = getattr(data_model, "use_output_constraints", True)
         self.last_acqf = None
+
+    def _sobo_spec(self, output_keys: Optional[Sequence[str]] = None):
+        """(terms, constraints) over the model outputs (``sobo_objective_spec``)."""
+        keys = list(self.model.output_keys) if output_keys is None else list(output_keys)
+        return sobo_objective_spec(self.domain.outputs, keys, self.experiments, additive=self._additive,
+                                   use_output_constraints=self.use_output_constraints)
+
+    def _draw_seed(self) -> int:
+        return int(torch.randint(0, 1000000, (1,), generator=self.gen).item())
 
     def _get_acqfs(self, n):
         af = self.acquisition_function
         if not isinstance(af, (dm.qEI, dm.qLogEI, dm.qNEI, dm.qLogNEI)):
             raise NotImplementedError(f"{type(af).__name__} is out of scope; use qLogNEI(), qNEI(), qLogEI() or qEI()")
-        target = self.domain.outputs.get_by_objective([MaximizeObjective, MinimizeObjective]).features[0]
-        if self.model.output_keys.index(target.key) != 0 or len(self.model.output_keys) != 1:
-            raise NotImplementedError("single-output SOBO only")
-        a, b = target.objective.affine()
+        terms, constraints = self._sobo_spec()
         X_train, X_pending = self.get_acqf_input_tensors()
         S = int(af.n_mc_samples)
+        m = len(self.model.output_keys)
+        if not (m == 1 and not constraints and len(terms) == 1 and terms[0][1] == ops.OBJ_AFFINE
+                and terms[0][2] == 1.0):
+            return self._get_general_acqfs(af, ops.SoboSpec(m, terms, constraints), X_train, X_pending, S)
+        a, b = terms[0][3], terms[0][4]
         if isinstance(af, (dm.qNEI, dm.qLogNEI)):
             # seed order of MoboStrategy's qNEHVI branch: prune seed (when pruning), then sampler seed
-            def draw_seed():
-                return int(torch.randint(0, 1000000, (1,), generator=self.gen).item())
-            prune_seed = draw_seed() if af.prune_baseline else 0
-            sampler_seed = draw_seed()
+            prune_seed = self._draw_seed() if af.prune_baseline else 0
+            sampler_seed = self._draw_seed()
             cls = QLogNEI if isinstance(af, dm.qLogNEI) else QNEI
             acqf = cls(self.model, self.model.X_raw, X_train, a, b, S=S, sampler_seed=sampler_seed,
                        prune_baseline=af.prune_baseline, prune_seed=prune_seed, X_pending_raw=X_pending)
             self.last_acqf = acqf
             return [acqf]
-        seed = int(torch.randint(0, 1000000, (1,), generator=self.gen).item())
+        seed = self._draw_seed()
         if isinstance(af, dm.qLogEI):
             acqf = QLogEI(self.model, X_train, a, b, S=S, seed=seed, X_pending_raw=X_pending)
             self.last_acqf = acqf
@@ -771,12 +849,36 @@ class SoboStrategy(BotorchStrategy):
         self.last_acqf = acqf
         return [acqf]
 
+    def _get_general_acqfs(self, af, spec: ops.SoboSpec, X_train, X_pending, S: int):
+        """Several model outputs, output constraints or a non-affine utility: the scalarised,
+        constraint-weighted chain (seed order as above)."""
+        if isinstance(af, (dm.qNEI, dm.qLogNEI)):
+            prune_seed = self._draw_seed() if af.prune_baseline else 0
+            sampler_seed = self._draw_seed()
+            cls = QSoboLogNEI if isinstance(af, dm.qLogNEI) else QSoboNEI
+            acqf = cls(self.model, self.model.X_raw, X_train, spec, S=S, sampler_seed=sampler_seed,
+                       prune_baseline=af.prune_baseline, prune_seed=prune_seed, X_pending_raw=X_pending)
+        else:
+            acqf = QSoboLogEI(self.model, X_train, spec, S=S, seed=self._draw_seed(), X_pending_raw=X_pending,
+                              log=isinstance(af, dm.qLogEI))
+        self.last_acqf = acqf
+        return [acqf]
+
+
+class AdditiveSoboStrategy(SoboStrategy):
+    """bofire/strategies/predictives/sobo.py:155-222 — the weighted sum u = sum w * g of the
+    objectives; with ``use_output_constraints`` the constrained objectives stay separate output
+    constraints, without it they enter the sum as sigmoid / target terms."""
+
+    _additive = True
+
 
 STRATEGY_MAP = {
     dm.QnehviStrategy: QnehviStrategy,
     dm.QehviStrategy: QehviStrategy,
     dm.MoboStrategy: MoboStrategy,
     dm.SoboStrategy: SoboStrategy,
+    dm.AdditiveSoboStrategy: AdditiveSoboStrategy,
     dm.RandomStrategy: RandomStrategy,
 }
 

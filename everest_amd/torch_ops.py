@@ -13,6 +13,8 @@ AcquisitionFunction.forward protocols called at bofire/strategies/predictives/bo
     torch.ops.everest_amd.qnehvi_backward(acq, X, grad_out) -> dX
     torch.classes.everest_amd.QneiAcq(state, model, log, tau_relu, tau_max, best, a, b, keep)
     torch.ops.everest_amd.qnei_forward / qnei_forward_backward / qnei_backward   (qNEI, qLogNEI, qLogEI)
+    torch.classes.everest_amd.QsoboAcq(state, model, log, tau_relu, tau_max, best, terms, constraints, keep)
+    torch.ops.everest_amd.qsobo_forward / qsobo_forward_backward   (scalarised / output-constrained SOBO)
 
 No fallback: a missing library raises NativeLibraryError."""
 from __future__ import annotations
@@ -80,6 +82,26 @@ class QneiFunction(torch.autograd.Function):
             return a
         ctx.save_for_backward(None)
         return ops.qnei_forward(acq, X)
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        (dX,) = ctx.saved_tensors
+        return dX * grad_out.reshape(-1, 1, 1), None
+
+
+class QsoboFunction(torch.autograd.Function):
+    """acq = QSoboNEI / QSoboLogNEI / QSoboLogEI(X), X b x q x d, through
+    torch.ops.everest_amd.qsobo_* on a torch.classes.everest_amd.QsoboAcq; as QneiFunction."""
+
+    @staticmethod
+    def forward(ctx, X: torch.Tensor, acq):
+        ops = load()
+        if ctx.needs_input_grad[0]:
+            a, dX = ops.qsobo_forward_backward(acq, X)
+            ctx.save_for_backward(dX)
+            return a
+        ctx.save_for_backward(None)
+        return ops.qsobo_forward(acq, X)
 
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):

@@ -466,7 +466,64 @@ int evr_qnei_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_genera
                   const evr_nei* nei, int b, const double* X, const double* gout, double* work, double* acq,
                   double* dX);
 
-/* The PyTorch-ROCm operators torch.ops.everest_amd.qnehvi_* (everest_amd/csrc/torch_ops.cpp)
+/* ---- scalarised single-objective scan with output constraints (sobo_scan.hip) -----------
+ * The step between the joint samples Y of q-point candidates and dY for a utility over several
+ * model outputs, u(y) = sum_t w_t g_t(y[out_t]) (1..EVR_SOBO_MAX_TERMS terms), and 0..16 output
+ * constraints c(y) = sign*(y[out] - thr) <= 0 with temperature eta ([upstream]
+ * SampleReducingMCAcquisitionFunction._apply_constraints as reached from BoFire's SoboStrategy /
+ * AdditiveSoboStrategy, bofire/strategies/predictives/sobo.py:42-222: the feasibility weighs
+ * every (sample, point) BEFORE the reduction over the q points):
+ *   plain (log = 0): acq_c = mean_s max_i [ (u_sci - best_s)_+ * exp(sum_c logsigmoid(-c/eta)) ]
+ *   log   (log = 1): acq_c = logmeanexp_s fatmax_i [ log fatplus(u_sci - best_s; tau_relu)
+ *                                                    + sum_c log_fatmoid(-c/eta) ; tau_max ]
+ * Term kinds: EVR_OBJ_AFFINE (p0*y + p1), EVR_OBJ_CLOSE_TO_TARGET (-|y - p0|^p1),
+ * EVR_OBJ_SIGMOID (1/(1+exp(-p0*(y-p1))); p0 = +steepness for MaximizeSigmoid, -steepness for
+ * MinimizeSigmoid) and EVR_OBJ_TARGET (sig(p0*(y-(p1-p2))) * (1 - sig(p0*(y-(p1+p2)))); p0 =
+ * steepness, p1 = target, p2 = tolerance) — the callables of bofire/utils/torch_tools.py:403-450.
+ * Y / dY: S x m_model x (b*q), Y[s][j][c*q + i] (the layout of the joint samples of
+ * evr_qng_eval).  flags (nullable, m_model x b ints): acq_c = NaN where any output's flag is
+ * set.  best / best_stride, gout and the plain-mode subgradients (strict improvement, first
+ * arg-max of the weighted value) are as in evr_nei_scan.  dY (nullable = forward only) is
+ * written in full: outputs no term or constraint reads get zeros.  The term / constraint arrays
+ * are HOST arrays (copied into the launch); best is on the device.  Forward and backward are
+ * ONE launch; results are bitwise reproducible. */
+#define EVR_OBJ_SIGMOID 2
+#define EVR_OBJ_TARGET 3
+#define EVR_SOBO_MAX_TERMS 8
+typedef struct {
+  int log;                  /* 0: plain (qNEI / qEI), 1: log (qLogNEI / qLogEI) */
+  double tau_relu;          /* log mode: fatplus temperature */
+  double tau_max;           /* log mode: fatmax temperature */
+  const double* best;       /* device: incumbent(s) in utility space */
+  int best_stride;          /* 1: S per-sample values, 0: one value */
+  int n_term;               /* 1..EVR_SOBO_MAX_TERMS */
+  const int* term_out;      /* n_term: model output index */
+  const int* term_kind;     /* n_term: EVR_OBJ_* */
+  const double* term_w;     /* n_term: weight in the sum */
+  const double* term_p0;
+  const double* term_p1;
+  const double* term_p2;    /* n_term: read by EVR_OBJ_TARGET only */
+  int n_con;                /* 0..16 */
+  const int* con_out;
+  const double* con_sign;
+  const double* con_thr;
+  const double* con_eta;
+} evr_sobo;
+int evr_sobo_scan(void* stream, int q, int m_model, int S, int b, const evr_sobo* sb, const double* Y,
+                  const int* flags, const double* gout, double* acq, double* dY);
+/* Full evaluation modelled on evr_qng_eval with the scan above in place of subsets / HVI /
+ * combine: kernel matrix over the m model outputs -> projection -> q x q Gram / jittered
+ * Cholesky / joint samples per (candidate, output) -> evr_sobo_scan -> (dX != NULL) analytic
+ * backward.  stm: model-side state (m = model outputs 1..8; cells unused); g: q and zq (device,
+ * S x q x m) only — its objective / constraint fields are not read.  X: (b*q) x d raw
+ * candidates; acq: b; dX: (b*q) x d. */
+long long evr_qsobo_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                      const evr_qnehvi_model* md, int b, int backward);
+int evr_qsobo_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                   const evr_sobo* sb, int b, const double* X, const double* gout, double* work, double* acq,
+                   double* dX);
+
+/* The PyTorch-ROCm operators torch.ops.everest_amd.qnehvi_*(everest_amd/csrc/torch_ops.cpp)
  * take a torch.classes.everest_amd.QnehviAcq: it copies the evr_qnehvi_state /
  * evr_qnehvi_model / evr_qn_general structs, holds references to the device tensors they
  * point into, and caches one plan per batch size (no raw addresses cross the boundary). */
