@@ -71,6 +71,17 @@ class EvrSobo(ctypes.Structure):
     ]
 
 
+class EvrParego(ctypes.Structure):
+    _fields_ = [
+        ("log", c_int), ("tau_relu", c_double), ("tau_max", c_double), ("best", c_void_p), ("best_stride", c_int),
+        ("alpha", c_double), ("n_term", c_int),
+        ("term_out", c_void_p), ("term_kind", c_void_p), ("term_p0", c_void_p), ("term_p1", c_void_p),
+        ("term_a", c_void_p), ("term_b", c_void_p),
+        ("n_con", c_int),
+        ("con_out", c_void_p), ("con_sign", c_void_p), ("con_thr", c_void_p), ("con_eta", c_void_p),
+    ]
+
+
 _SIGS = {
     "evr_version": ([], c_int),
     "evr_last_error": ([], c_char_p),
@@ -187,6 +198,11 @@ _SIGS = {
                                      c_int], c_longlong),
     "evr_qsobo_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
                         POINTER(EvrSobo), c_int] + [c_void_p] * 5, c_int),
+    "evr_parego_scan": ([c_void_p, c_int, c_int, c_int, c_int, POINTER(EvrParego)] + [c_void_p] * 5, c_int),
+    "evr_qparego_workspace_doubles": ([POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
+                                       c_int, c_int], c_longlong),
+    "evr_qparego_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
+                          POINTER(EvrParego), c_int] + [c_void_p] * 5, c_int),
     "evr_objective_general": ([c_void_p, c_int, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 4, c_int),
     "evr_objective_weights": ([c_void_p, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 3, c_int),
     "evr_cells_kd_limits": ([c_int, c_int, c_int, c_void_p], c_int),

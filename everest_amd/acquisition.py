@@ -1237,9 +1237,17 @@ class _SoboAcqf(_NeiAcqf):
     SampleReducingMCAcquisitionFunction._apply_constraints weighs every (sample, point) before
     the reduction over q, so the hypervolume chain's q-subset weighting does not apply.
     Subclasses set gp, dev, S, M, nb, spec and the incumbent(s) ``best`` and call _finish_sobo.
+    The spec decides the scan: an ops.SoboSpec runs evr_qsobo_eval, an ops.ParegoSpec (the
+    QParego* classes) evr_qparego_eval with the augmented Chebyshev scan of parego_scan.hip;
+    construction, incumbents and pruning only use the spec's utility / feasible.
 
     BoTorch is not importable offline: the incumbent's mean - 6 sigma fallback and the constrained
     prune are restated from memory of BoTorch and are parity-unpinned against it."""
+
+    @property
+    def _parego(self) -> bool:
+        """Dispatch on the spec: an ops.ParegoSpec runs the augmented Chebyshev scan."""
+        return isinstance(self.spec, ops.ParegoSpec)
 
     @staticmethod
     def _check_model(gp: GPBatch, spec: "ops.SoboSpec", name: str):
@@ -1275,20 +1283,22 @@ class _SoboAcqf(_NeiAcqf):
         torch.cuda.synchronize(self.dev)
 
     def _general(self, X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
-        """X: b x q x d -> (acq (b), dX b x q x d | None) through evr_qsobo_eval."""
+        """X: b x q x d -> (acq (b), dX b x q x d | None) through evr_qsobo_eval (evr_qparego_eval
+        for an ops.ParegoSpec)."""
         b, q, d = X.shape
         X = self._joint(X)
         qq = X.shape[1]
         g = _native.EvrQnGeneral()
         g.q, g.zq = int(qq), self._zq(qq).data_ptr()
-        acq, dX = ops.qsobo_eval(self.state, g, self.model, self.sb, X.reshape(b * qq, d).contiguous(), backward,
-                                 gout)
+        ev = ops.qparego_eval if self._parego else ops.qsobo_eval
+        acq, dX = ev(self.state, g, self.model, self.sb, X.reshape(b * qq, d).contiguous(), backward, gout)
         if dX is not None:
             dX = dX.view(b, qq, d)[:, :q].contiguous()
         return acq, dX
 
     def _torch_acq(self, q: int, fast: bool = False):
-        """The torch.classes.everest_amd.QsoboAcq behind torch.ops.everest_amd.qsobo_*."""
+        """The torch.classes.everest_amd.QsoboAcq behind torch.ops.everest_amd.qsobo_* (QparegoAcq
+        and qparego_* for an ops.ParegoSpec)."""
         from . import torch_ops
 
         torch_ops.load()
@@ -1298,8 +1308,13 @@ class _SoboAcqf(_NeiAcqf):
                 return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8)
             terms = torch.tensor(self.spec.terms, dtype=torch.float64).reshape(-1, 6)
             cons = torch.tensor(self.spec.constraints, dtype=torch.float64).reshape(-1, 4)
-            acq = torch.classes.everest_amd.QsoboAcq(raw(self.state), raw(self.model), self.log_acqf, self.tau_relu,
-                                                     self.tau_max, self.best, terms, cons, self._device_tensors())
+            cls = torch.classes.everest_amd
+            if self._parego:
+                acq = cls.QparegoAcq(raw(self.state), raw(self.model), self.log_acqf, self.tau_relu, self.tau_max,
+                                     self.best, self.spec.alpha, terms, cons, self._device_tensors())
+            else:
+                acq = cls.QsoboAcq(raw(self.state), raw(self.model), self.log_acqf, self.tau_relu, self.tau_max,
+                                   self.best, terms, cons, self._device_tensors())
             self._torch_sobo = acq
         done = self.__dict__.setdefault("_torch_sobo_q", set())
         if q not in done:
@@ -1310,10 +1325,10 @@ class _SoboAcqf(_NeiAcqf):
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
         """X (b x q x d, or b x d for q = 1) -> acq (b), differentiable through the device
         backward (torch.ops.everest_amd.qsobo_forward / qsobo_forward_backward)."""
-        from .torch_ops import QsoboFunction
+        from .torch_ops import QparegoFunction, QsoboFunction
 
         X3 = self._joint(self._split(X)[0]).contiguous()
-        return QsoboFunction.apply(X3, self._torch_acq(X3.shape[1]))
+        return (QparegoFunction if self._parego else QsoboFunction).apply(X3, self._torch_acq(X3.shape[1]))
 
 
 class QSoboNEI(_SoboAcqf):
@@ -1459,6 +1474,41 @@ class QSoboLogEI(_SoboAcqf):
 
     def _draw_zq(self, q: int) -> torch.Tensor:
         return ops.sobol_normal(self.S, q * self.m, self.sampler_seed, self.dev)
+
+
+
+def _need_parego(spec, name: str):
+    if not isinstance(spec, ops.ParegoSpec):
+        raise TypeError(f"{name} needs an ops.ParegoSpec, got {type(spec).__name__}")
+
+
+class QParegoNEI(QSoboNEI):
+    """Device qNEI of qParEGO — [upstream] get_acquisition_function("qNEI") over a
+    GenericMCObjective of get_chebyshev_scalarization, as QparegoStrategy._get_acqfs builds it
+    (bofire/strategies/predictives/qparego.py:30-140): the QSoboNEI construction (baseline root,
+    prune, per-sample incumbent, M, pending points, base samples) with the utility
+    u(y) = min_k t_k(y) + alpha sum_k t_k(y) of ``spec`` (ops.ParegoSpec) and the scan of
+    parego_scan.hip.  Parity-unpinned like QSoboNEI."""
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, X_baseline_raw: np.ndarray, spec: "ops.ParegoSpec",
+                 **kw):
+        _need_parego(spec, type(self).__name__)
+        super().__init__(gp, X_train_raw, X_baseline_raw, spec, **kw)
+
+
+class QParegoLogNEI(QParegoNEI):
+    """Device qLogNEI (fat = True) of qParEGO: QParegoNEI with the log scan."""
+
+    _LOG = True
+
+
+class QParegoLogEI(QSoboLogEI):
+    """Device qLogEI (``log=False``: qEI) of qParEGO: the QSoboLogEI construction with the
+    augmented Chebyshev utility of ``spec`` (ops.ParegoSpec)."""
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, spec: "ops.ParegoSpec", **kw):
+        _need_parego(spec, "QParegoLogEI")
+        super().__init__(gp, X_train_raw, spec, **kw)
 
 
 class QEI:

@@ -1210,9 +1210,11 @@ int evr_qlog_eval(void* stream, const evr_qnehvi_state* stm, const evr_qnehvi_st
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------
-// qNEI / qLogNEI / qLogEI: the chain of evr_qng_eval at one output with the improvement scan
-// of nei_scan.hip between the joint samples and their adjoint — no subset expansion, no
-// cells, one scan launch (forward and backward) instead of subsets + HVI scan + combine.
+// qNEI / qLogNEI / qLogEI, their scalarised / constrained forms and qParEGO: the chain of
+// evr_qng_eval with an improvement scan (nei_scan.hip at one output; sobo_scan.hip and
+// parego_scan.hip over m outputs) between the joint samples and their adjoint — no subset
+// expansion, no cells, one scan launch (forward and backward) instead of subsets + HVI scan +
+// combine.
 // ---------------------------------------------------------------------------------------
 namespace evr {
 
@@ -1221,6 +1223,8 @@ int nei_scan_launch(hipStream_t s, int q, bool log_mode, int S, int b, const dou
                     const double* gout, double* acq, double* dY);
 int sobo_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_sobo* sb, const double* Y,
                      const int* flags, const double* gout, double* acq, double* dY);
+int parego_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_parego* pg, const double* Y,
+                       const int* flags, const double* gout, double* acq, double* dY);
 
 struct QnLayout {
   size_t Kx, R, P, Wf, Y, Lq, flags, dY, cf, dKqq, cm, gR, dKx, Wb, kg, total;
@@ -1258,107 +1262,20 @@ static QnLayout qn_layout(const evr_qnehvi_state* stm, int q, int d, int b, bool
   return L;
 }
 
-}  // namespace evr
-
-extern "C" {
-
-long long evr_qnei_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
-                                     const evr_qnehvi_model* md, int b, int backward) {
-  if (!stm || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q || stm->m != 1) return 0;
-  return (long long)qn_layout(stm, g->q, md->d, b, backward != 0).total;
-}
-
-int evr_qnei_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
-                  const evr_nei* nei, int b, const double* X, const double* gout, double* work, double* acq,
-                  double* dX) {
-  EVR_CHECK(stm && g && md && nei, "evr_qnei_eval: null argument");
-  EVR_CHECK(g->q >= 1 && g->q <= EVR_QNG_MAX_Q, "evr_qnei_eval: q = %d outside 1..%d", g->q, EVR_QNG_MAX_Q);
-  EVR_CHECK(stm->m == 1 && g->m_obj == 1 && g->n_con == 0 && g->obj_out && g->obj_kind && g->obj_p0 && g->obj_p1 &&
-                g->obj_out[0] == 0 && g->obj_kind[0] == EVR_OBJ_AFFINE,
-            "evr_qnei_eval: one model output with one affine objective and no output constraints");
+// The chain the three entry points below share: kernel matrix -> projection -> q x q Gram /
+// jittered Cholesky / joint samples per (candidate, output) -> scan(Y, flags, dY) -> (dX != NULL)
+// analytic backward.  The entry points differ only in their checks and the scan they launch.
+template <class Scan>
+static int qn_chain(const char* who, hipStream_t s, const evr_qnehvi_state* stm, const evr_qn_general* g,
+                    const evr_qnehvi_model* md, int b, const double* X, double* work, double* acq, double* dX,
+                    Scan scan) {
+  EVR_CHECK(g->q >= 1 && g->q <= EVR_QNG_MAX_Q, "%s: q = %d outside 1..%d", who, g->q, EVR_QNG_MAX_Q);
+  EVR_CHECK(stm->m >= 1 && stm->m <= QG_MAXM, "%s: %d model outputs outside 1..%d", who, stm->m, QG_MAXM);
   EVR_CHECK(md->n == stm->n && md->d >= 1 && md->M && md->Xn && md->lengthscales && g->zq && stm->c && stm->ym &&
                 stm->ys && stm->kxx && stm->S >= 1,
-            "evr_qnei_eval: inconsistent model / state");
-  EVR_CHECK(nei->best && (nei->best_stride == 0 || nei->best_stride == 1), "evr_qnei_eval: bad incumbent");
-  EVR_CHECK(X && work && acq && b >= 0, "evr_qnei_eval: bad arguments");
+            "%s: inconsistent model / state", who);
+  EVR_CHECK(X && work && acq && b >= 0, "%s: bad arguments", who);
   if (b == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  const int q = g->q, n = stm->n, d = md->d, S = stm->S;
-  const int bq = b * q;
-  const bool backward = dX != nullptr;
-  const QnLayout L = qn_layout(stm, q, d, b, backward);
-  double* w = work;
-  double* Kx = w + L.Kx;
-  double* R = w + L.R;
-  double* Y = w + L.Y;
-  double* Lq = w + L.Lq;
-  int* flags = (int*)(w + L.flags);
-  double* dY = backward ? w + L.dY : nullptr;
-  const QgDims dm{n, stm->nb, qn_nh(stm), S, 1, b};
-  if (int rc = evr_kernel_matrix(s, md->kind, 1, n, bq, d, md->Xn, nullptr, nullptr, X, md->shift, md->scale,
-                                 md->lengthscales, nullptr, nullptr, Kx))
-    return rc;
-  if (int rc = proj_forward(s, stm, bq, md->M, Kx, R, w + L.P, L.Wf != L.Y ? w + L.Wf : nullptr)) return rc;
-#define GO(QQ)                                                                                                   \
-  qg_gram_samples<QQ><<<dim3(b, 1), 256, 0, s>>>(dm, md->kind, d, R, X, md->lengthscales, md->shift, md->scale,   \
-                                                 stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags);       \
-  EVR_LAUNCH_CHECK()
-  QG_SWITCH(q, GO);
-#undef GO
-  if (int rc = nei_scan_launch(s, q, nei->log != 0, S, b, Y, nei->best, nei->best_stride, g->obj_p0[0], g->obj_p1[0],
-                               nei->tau_relu, nei->tau_max, flags, gout, acq, dY))
-    return rc;
-  if (!backward) return 0;
-  double* cf = w + L.cf;
-  double* dKqq = w + L.dKqq;
-  double* cm = w + L.cm;
-  double* gR = w + L.gR;
-  double* dKx = w + L.dKx;
-  const int Rr = qn_rows(stm);
-#define GO(QQ)                                                                                                   \
-  qg_samples_bwd<QQ><<<dim3(b, 1), 256, 0, s>>>(dm, dY, g->zq, Lq, stm->ys, cf, dKqq, cm);                        \
-  EVR_LAUNCH_CHECK();                                                                                            \
-  qg_gen_gr<QQ><<<dim3(Rr, cdiv(bq, 256)), 256, 0, s>>>(dm, R, dY, cf, cm, stm->ys, gR);                          \
-  EVR_LAUNCH_CHECK()
-  QG_SWITCH(q, GO);
-#undef GO
-  if (int rc = dg_gemm(s, true, n, bq, Rr, 1.0, md->M, n, (long long)Rr * n, gR, bq, (long long)Rr * bq, 0.0, dKx, bq,
-                       (long long)n * bq, 1, w + L.Wb))
-    return rc;
-  if (int rc = kcross_grad_launch(s, md->kind, 1, n, bq, d, md->Xn, nullptr, nullptr, X, md->shift, md->scale,
-                                  md->lengthscales, nullptr, dKx, dX, w + L.kg))
-    return rc;
-  if (q > 1) {
-#define GO(QQ)                                                                                                   \
-  qg_kqq_grad<QQ><<<cdiv(bq, 64), 64, 0, s>>>(b, 1, d, md->kind, X, md->lengthscales, md->shift, md->scale,       \
-                                              stm->kxx, dKqq, dX);                                               \
-  EVR_LAUNCH_CHECK()
-    QG_SWITCH(q, GO);
-#undef GO
-  }
-  return 0;
-}
-
-// qSobo*: the same chain over m model outputs with the scalarised, constraint-weighted scan of
-// sobo_scan.hip (SoboStrategy with constrained objectives, AdditiveSoboStrategy).
-long long evr_qsobo_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
-                                      const evr_qnehvi_model* md, int b, int backward) {
-  if (!stm || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q || stm->m < 1 || stm->m > QG_MAXM) return 0;
-  return (long long)qn_layout(stm, g->q, md->d, b, backward != 0).total;
-}
-
-int evr_qsobo_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
-                   const evr_sobo* sb, int b, const double* X, const double* gout, double* work, double* acq,
-                   double* dX) {
-  EVR_CHECK(stm && g && md && sb, "evr_qsobo_eval: null argument");
-  EVR_CHECK(g->q >= 1 && g->q <= EVR_QNG_MAX_Q, "evr_qsobo_eval: q = %d outside 1..%d", g->q, EVR_QNG_MAX_Q);
-  EVR_CHECK(stm->m >= 1 && stm->m <= QG_MAXM, "evr_qsobo_eval: %d model outputs outside 1..%d", stm->m, QG_MAXM);
-  EVR_CHECK(md->n == stm->n && md->d >= 1 && md->M && md->Xn && md->lengthscales && g->zq && stm->c && stm->ym &&
-                stm->ys && stm->kxx && stm->S >= 1,
-            "evr_qsobo_eval: inconsistent model / state");
-  EVR_CHECK(X && work && acq && b >= 0, "evr_qsobo_eval: bad arguments");
-  if (b == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
   const int q = g->q, m = stm->m, n = stm->n, d = md->d, S = stm->S;
   const int bq = b * q;
   const bool backward = dX != nullptr;
@@ -1381,7 +1298,7 @@ int evr_qsobo_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_gener
   EVR_LAUNCH_CHECK()
   QG_SWITCH(q, GO);
 #undef GO
-  if (int rc = sobo_scan_launch(s, q, m, S, b, sb, Y, flags, gout, acq, dY)) return rc;
+  if (int rc = scan(q, m, S, Y, flags, dY)) return rc;
   if (!backward) return 0;
   double* cf = w + L.cf;
   double* dKqq = w + L.dKqq;
@@ -1411,6 +1328,73 @@ int evr_qsobo_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_gener
 #undef GO
   }
   return 0;
+}
+
+}  // namespace evr
+
+extern "C" {
+
+long long evr_qnei_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                     const evr_qnehvi_model* md, int b, int backward) {
+  if (!stm || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q || stm->m != 1) return 0;
+  return (long long)qn_layout(stm, g->q, md->d, b, backward != 0).total;
+}
+
+int evr_qnei_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                  const evr_nei* nei, int b, const double* X, const double* gout, double* work, double* acq,
+                  double* dX) {
+  EVR_CHECK(stm && g && md && nei, "evr_qnei_eval: null argument");
+  EVR_CHECK(stm->m == 1 && g->m_obj == 1 && g->n_con == 0 && g->obj_out && g->obj_kind && g->obj_p0 && g->obj_p1 &&
+                g->obj_out[0] == 0 && g->obj_kind[0] == EVR_OBJ_AFFINE,
+            "evr_qnei_eval: one model output with one affine objective and no output constraints");
+  EVR_CHECK(nei->best && (nei->best_stride == 0 || nei->best_stride == 1), "evr_qnei_eval: bad incumbent");
+  hipStream_t s = (hipStream_t)stream;
+  return qn_chain("evr_qnei_eval", s, stm, g, md, b, X, work, acq, dX,
+                  [&](int q, int, int S, const double* Y, const int* flags, double* dY) {
+                    return nei_scan_launch(s, q, nei->log != 0, S, b, Y, nei->best, nei->best_stride, g->obj_p0[0],
+                                           g->obj_p1[0], nei->tau_relu, nei->tau_max, flags, gout, acq, dY);
+                  });
+}
+
+// qSobo*: the chain over m model outputs with the scalarised, constraint-weighted scan of
+// sobo_scan.hip (SoboStrategy with constrained objectives, AdditiveSoboStrategy).
+static long long qn_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                      const evr_qnehvi_model* md, int b, int backward) {
+  if (!stm || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q || stm->m < 1 || stm->m > QG_MAXM) return 0;
+  return (long long)qn_layout(stm, g->q, md->d, b, backward != 0).total;
+}
+
+long long evr_qsobo_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                      const evr_qnehvi_model* md, int b, int backward) {
+  return qn_workspace_doubles(stm, g, md, b, backward);
+}
+
+int evr_qsobo_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                   const evr_sobo* sb, int b, const double* X, const double* gout, double* work, double* acq,
+                   double* dX) {
+  EVR_CHECK(stm && g && md && sb, "evr_qsobo_eval: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  return qn_chain("evr_qsobo_eval", s, stm, g, md, b, X, work, acq, dX,
+                  [&](int q, int m, int S, const double* Y, const int* flags, double* dY) {
+                    return sobo_scan_launch(s, q, m, S, b, sb, Y, flags, gout, acq, dY);
+                  });
+}
+
+// qParego*: the chain with the augmented Chebyshev scan of parego_scan.hip (QparegoStrategy).
+long long evr_qparego_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                        const evr_qnehvi_model* md, int b, int backward) {
+  return qn_workspace_doubles(stm, g, md, b, backward);
+}
+
+int evr_qparego_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                     const evr_parego* pg, int b, const double* X, const double* gout, double* work, double* acq,
+                     double* dX) {
+  EVR_CHECK(stm && g && md && pg, "evr_qparego_eval: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  return qn_chain("evr_qparego_eval", s, stm, g, md, b, X, work, acq, dX,
+                  [&](int q, int m, int S, const double* Y, const int* flags, double* dY) {
+                    return parego_scan_launch(s, q, m, S, b, pg, Y, flags, gout, acq, dY);
+                  });
 }
 
 }  // extern "C"

@@ -1,0 +1,136 @@
+// Pieces shared by the utility scans over several model outputs (sobo_scan.hip: sum of terms;
+// parego_scan.hip: augmented Chebyshev): the by-value term / constraint table, the per-term
+// callables, and the same steps sobo_scan's sb_points / sb_sample / backward take around the
+// utility, as functions of their own: the summed log feasibilities of the q points, the reduction
+// over the q points of a (sample, candidate), and the constraint slopes of one output row.
+// sobo_scan.hip keeps its own fused copies of those three: its device code is unchanged.
+#pragma once
+#include "common.hpp"
+#include "ns_reduce.hpp"
+#include "qg_obj.hpp"
+#include "../../include/everest_amd.h"
+
+namespace evr {
+
+static_assert(EVR_SOBO_MAX_TERMS == QG_MAXM, "the term table reuses QgObj's objective slots");
+
+// terms (QgObj's objective slots plus weight and third parameter) and constraints, by value
+struct SbTab {
+  QgObj o;
+  double w[QG_MAXM], p2[QG_MAXM];
+};
+
+__device__ __forceinline__ double sb_term(const SbTab& t, int k, double y) {
+  const int kind = t.o.ok[k];
+  if (kind == EVR_OBJ_AFFINE || kind == EVR_OBJ_CLOSE_TO_TARGET) return qg_obj(t.o, k, y);
+  const double st = t.o.p0[k];
+  if (kind == EVR_OBJ_SIGMOID) return qg_sig(st * (y - t.o.p1[k]));
+  // target: sig(st (y - (tv - tol))) * (1 - sig(st (y - (tv + tol))))
+  return qg_sig(st * (y - (t.o.p1[k] - t.p2[k]))) * qg_sig(-st * (y - (t.o.p1[k] + t.p2[k])));
+}
+
+__device__ __forceinline__ double sb_dterm(const SbTab& t, int k, double y) {
+  const int kind = t.o.ok[k];
+  if (kind == EVR_OBJ_AFFINE || kind == EVR_OBJ_CLOSE_TO_TARGET) return qg_dobj(t.o, k, y);
+  const double st = t.o.p0[k];
+  if (kind == EVR_OBJ_SIGMOID) {
+    const double x = st * (y - t.o.p1[k]);
+    return st * qg_sig(x) * qg_sig(-x);
+  }
+  const double x1 = st * (y - (t.o.p1[k] - t.p2[k])), x2 = st * (y - (t.o.p1[k] + t.p2[k]));
+  return st * qg_sig(x1) * qg_sig(-x2) * (qg_sig(-x1) - qg_sig(x2));
+}
+
+// summed log feasibilities of the Q points of one (sample, candidate), added to lw (log-sigmoid
+// in plain mode, log-fatmoid in log mode).  Ys: the output-0 sample of point 0, outputs `st`
+// doubles apart.  The constraint loop is the outer one: one set of scalar table reads per
+// constraint, whatever Q.
+template <int Q, bool LOG>
+__device__ __forceinline__ void sb_feas(const QgObj& o, const double* __restrict__ Ys, size_t st, double* lw) {
+  for (int e = 0; e < o.nc; ++e) {
+    const double* Ye = Ys + (size_t)o.co[e] * st;
+    const double cs = o.cs[e], ct = o.ct[e], ce = o.ce[e];
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+      const double cval = cs * (Ye[i] - ct);
+      lw[i] += LOG ? qg_log_fatmoid(-cval / ce) : qg_logsig(-cval / ce);
+    }
+  }
+}
+
+// per (sample, candidate), from the Q utilities u and summed log feasibilities lw (both
+// overwritten): the value entering the sample reduction and, with `du`, its slopes with respect
+// to the utilities (du) and the log feasibilities (dl).  con: whether any constraint exists.
+template <int Q, bool LOG>
+__device__ __forceinline__ double sb_reduce(double* u, double* lw, bool con, double best, double tr, double tm,
+                                            double* du, double* dl) {
+  if (!LOG) {
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+      const double v = u[i] - best;
+      lw[i] = con ? exp(lw[i]) : 1.0;
+      u[i] = (v > 0.0 ? v : 0.0) * lw[i];
+    }
+    double mx = u[0];
+    int am = 0;
+#pragma unroll
+    for (int i = 1; i < Q; ++i)
+      if (u[i] > mx) {   // first arg-max (torch.max)
+        mx = u[i];
+        am = i;
+      }
+    const bool on = mx > 0.0;
+    if (du)
+#pragma unroll
+      for (int i = 0; i < Q; ++i) {
+        du[i] = (on && i == am) ? lw[i] : 0.0;     // d [(u - best)_+ W] / d u
+        dl[i] = (on && i == am) ? u[i] : 0.0;      // d [(u - best)_+ exp(lw)] / d lw
+      }
+    return on ? mx : 0.0;
+  }
+  double da[Q];
+#pragma unroll
+  for (int i = 0; i < Q; ++i) u[i] = log_fatplus(u[i] - best, tr, du ? &da[i] : nullptr) + lw[i];
+  const double v = ns_fatmax<Q>(u, tm, du ? dl : nullptr);
+  if (du)
+#pragma unroll
+    for (int i = 0; i < Q; ++i) du[i] = dl[i] * da[i];
+  return v;
+}
+
+// backward: the slopes of the constraints reading output j, added to acc (Yj: the output-j
+// sample of point 0; dl: the slopes with respect to the summed log feasibilities)
+template <int Q, bool LOG>
+__device__ __forceinline__ void sb_dfeas(const QgObj& o, int j, const double* __restrict__ Yj, const double* dl,
+                                         double* acc) {
+  for (int e = 0; e < o.nc; ++e) {
+    if (o.co[e] != j) continue;
+    const double cs = o.cs[e], ct = o.ct[e], ce = o.ce[e];
+    const double sc = -cs / ce;   // d (-c / eta) / d y
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+      const double x = -(cs * (Yj[i] - ct)) / ce;
+      acc[i] += dl[i] * (LOG ? qg_dlog_fatmoid(x) : qg_sig(-x)) * sc;
+    }
+  }
+}
+
+// shared by the launchers: the q switch over the compiled instantiations
+#define SB_SWITCH(q, MACRO, NAME)                                           \
+  switch (q) {                                                              \
+    case 1: MACRO(1); break;                                                \
+    case 2: MACRO(2); break;                                                \
+    case 3: MACRO(3); break;                                                \
+    case 4: MACRO(4); break;                                                \
+    case 5: MACRO(5); break;                                                \
+    case 6: MACRO(6); break;                                                \
+    case 7: MACRO(7); break;                                                \
+    case 8: MACRO(8); break;                                                \
+    case 9: MACRO(9); break;                                                \
+    case 10: MACRO(10); break;                                              \
+    case 11: MACRO(11); break;                                              \
+    case 12: MACRO(12); break;                                              \
+    default: EVR_CHECK(false, NAME ": q = %d not supported", q);            \
+  }
+
+}  // namespace evr

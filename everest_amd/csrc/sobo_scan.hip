@@ -28,41 +28,9 @@
 //
 // With m = 1, one affine term of weight 1 and no constraints every operation added here is exact
 // (0.0 + 1.0 g, a + 0.0, x * 1.0), so the results equal nei_scan's bit for bit.
-#include "common.hpp"
-#include "ns_reduce.hpp"
-#include "qg_obj.hpp"
-#include "../../include/everest_amd.h"
+#include "sb_common.hpp"
 
 namespace evr {
-
-static_assert(EVR_SOBO_MAX_TERMS == QG_MAXM, "the term table reuses QgObj's objective slots");
-
-// terms (QgObj's objective slots plus weight and third parameter) and constraints, by value
-struct SbTab {
-  QgObj o;
-  double w[QG_MAXM], p2[QG_MAXM];
-};
-
-__device__ __forceinline__ double sb_term(const SbTab& t, int k, double y) {
-  const int kind = t.o.ok[k];
-  if (kind == EVR_OBJ_AFFINE || kind == EVR_OBJ_CLOSE_TO_TARGET) return qg_obj(t.o, k, y);
-  const double st = t.o.p0[k];
-  if (kind == EVR_OBJ_SIGMOID) return qg_sig(st * (y - t.o.p1[k]));
-  // target: sig(st (y - (tv - tol))) * (1 - sig(st (y - (tv + tol))))
-  return qg_sig(st * (y - (t.o.p1[k] - t.p2[k]))) * qg_sig(-st * (y - (t.o.p1[k] + t.p2[k])));
-}
-
-__device__ __forceinline__ double sb_dterm(const SbTab& t, int k, double y) {
-  const int kind = t.o.ok[k];
-  if (kind == EVR_OBJ_AFFINE || kind == EVR_OBJ_CLOSE_TO_TARGET) return qg_dobj(t.o, k, y);
-  const double st = t.o.p0[k];
-  if (kind == EVR_OBJ_SIGMOID) {
-    const double x = st * (y - t.o.p1[k]);
-    return st * qg_sig(x) * qg_sig(-x);
-  }
-  const double x1 = st * (y - (t.o.p1[k] - t.p2[k])), x2 = st * (y - (t.o.p1[k] + t.p2[k]));
-  return st * qg_sig(x1) * qg_sig(-x2) * (qg_sig(-x1) - qg_sig(x2));
-}
 
 // the Q points of one (sample, candidate) (Ys: the output-0 sample of point 0, outputs `st`
 // doubles apart): utilities and summed log feasibilities (log-sigmoid in plain mode, log-fatmoid
@@ -265,23 +233,6 @@ static int sb_params(const evr_sobo* sb, int m_model, SbTab* t) {
   return 0;
 }
 
-#define SB_SWITCH(q, MACRO)                                                  \
-  switch (q) {                                                              \
-    case 1: MACRO(1); break;                                                \
-    case 2: MACRO(2); break;                                                \
-    case 3: MACRO(3); break;                                                \
-    case 4: MACRO(4); break;                                                \
-    case 5: MACRO(5); break;                                                \
-    case 6: MACRO(6); break;                                                \
-    case 7: MACRO(7); break;                                                \
-    case 8: MACRO(8); break;                                                \
-    case 9: MACRO(9); break;                                                \
-    case 10: MACRO(10); break;                                              \
-    case 11: MACRO(11); break;                                              \
-    case 12: MACRO(12); break;                                              \
-    default: EVR_CHECK(false, "sobo_scan: q = %d not supported", q);        \
-  }
-
 int sobo_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_sobo* sb, const double* Y,
                      const int* flags, const double* gout, double* acq, double* dY) {
   EVR_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "sobo_scan: q = %d outside 1..%d", q, EVR_QNG_MAX_Q);
@@ -307,7 +258,7 @@ int sobo_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_
                                                                  dY);                                               \
   }                                                                                                                 \
   EVR_LAUNCH_CHECK()
-  SB_SWITCH(q, GO);
+  SB_SWITCH(q, GO, "sobo_scan");
 #undef GO
   return 0;
 }

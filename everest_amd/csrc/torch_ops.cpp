@@ -478,9 +478,123 @@ std::tuple<at::Tensor, at::Tensor> qsobo_forward_backward(const SoboPtr& acq, co
   return acq->eval(X, true);
 }
 
+// ---------------------------------------------------------------------------------------
+// The acquisition behind torch.ops.everest_amd.qparego_*: qParEGO's qNEI / qLogNEI / qLogEI /
+// qEI over several model outputs (augmented Chebyshev utility, output constraints) through
+// evr_qparego_eval.  Ownership as in QsoboAcq.
+// ---------------------------------------------------------------------------------------
+struct QparegoAcq : torch::CustomClassHolder {
+  evr_qnehvi_state stm{};
+  evr_qnehvi_model md{};
+  evr_parego pg{};
+  std::vector<int> to, tk, co;
+  std::vector<double> tp0, tp1, ta, tb, cs, ct, ce;
+  at::Tensor best;
+  std::vector<at::Tensor> keep;
+  std::map<int64_t, at::Tensor> zqs;
+  int64_t n_evals = 0;
+
+  // terms: n_term x 6 doubles (out, kind, p0, p1, A, B); cons: n_con x 4 doubles (out, sign, thr, eta)
+  QparegoAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
+             const at::Tensor& best_, double alpha, const at::Tensor& terms_, const at::Tensor& cons_,
+             std::vector<at::Tensor> keep_)
+      : keep(std::move(keep_)) {
+    stm = QnehviAcq::from_bytes<evr_qnehvi_state>(stm_b, "model-side state");
+    md = QnehviAcq::from_bytes<evr_qnehvi_model>(md_b, "model");
+    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m >= 1,
+                "QparegoAcq: inconsistent model");
+    best = dev64(best_, "best");
+    TORCH_CHECK(best.numel() == 1 || best.numel() == stm.S, "QparegoAcq: best needs 1 or S values");
+    auto T = terms_.to(at::kCPU, at::kDouble).contiguous();
+    auto C = cons_.to(at::kCPU, at::kDouble).contiguous();
+    TORCH_CHECK(T.dim() == 2 && T.size(1) == 6 && T.size(0) >= 2 && T.size(0) <= EVR_SOBO_MAX_TERMS,
+                "QparegoAcq: terms must be n_term x 6, 2..", EVR_SOBO_MAX_TERMS, " rows");
+    TORCH_CHECK(C.numel() == 0 || (C.dim() == 2 && C.size(1) == 4), "QparegoAcq: constraints must be n_con x 4");
+    const double* t = T.data_ptr<double>();
+    for (int64_t k = 0; k < T.size(0); ++k, t += 6) {
+      to.push_back((int)t[0]);
+      tk.push_back((int)t[1]);
+      tp0.push_back(t[2]);
+      tp1.push_back(t[3]);
+      ta.push_back(t[4]);
+      tb.push_back(t[5]);
+    }
+    const int64_t nc = C.numel() / 4;
+    const double* c = nc ? C.data_ptr<double>() : nullptr;
+    for (int64_t e = 0; e < nc; ++e, c += 4) {
+      co.push_back((int)c[0]);
+      cs.push_back(c[1]);
+      ct.push_back(c[2]);
+      ce.push_back(c[3]);
+    }
+    pg.log = log_ ? 1 : 0;
+    pg.tau_relu = tau_relu;
+    pg.tau_max = tau_max;
+    pg.best = best.data_ptr<double>();
+    pg.best_stride = best.numel() == 1 ? 0 : 1;
+    pg.alpha = alpha;
+    pg.n_term = (int)to.size();
+    pg.term_out = to.data();
+    pg.term_kind = tk.data();
+    pg.term_p0 = tp0.data();
+    pg.term_p1 = tp1.data();
+    pg.term_a = ta.data();
+    pg.term_b = tb.data();
+    pg.n_con = (int)nc;
+    pg.con_out = nc ? co.data() : nullptr;
+    pg.con_sign = nc ? cs.data() : nullptr;
+    pg.con_thr = nc ? ct.data() : nullptr;
+    pg.con_eta = nc ? ce.data() : nullptr;
+  }
+
+  void set_samples(int64_t q, const at::Tensor& zq) {
+    TORCH_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "QparegoAcq.set_samples: q = ", q, " outside 1..", EVR_QNG_MAX_Q);
+    auto z = dev64(zq, "zq");
+    TORCH_CHECK(z.numel() == (int64_t)stm.S * q * stm.m, "QparegoAcq.set_samples: zq must be S x q x m");
+    zqs[q] = z;
+  }
+
+  std::tuple<at::Tensor, at::Tensor> eval(const at::Tensor& X_, bool backward) {
+    auto X = dev64(X_, "X");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+    hipStream_t s = cur_stream();
+    TORCH_CHECK(X.dim() == 3 && X.size(2) == md.d, "qparego: X must be b x q x d");
+    const int64_t b = X.size(0), q = X.size(1);
+    auto it = zqs.find(q);
+    TORCH_CHECK(it != zqs.end(), "qparego: no base samples set for q = ", q);
+    evr_qn_general g{};
+    g.q = (int)q;
+    g.zq = it->second.data_ptr<double>();
+    auto acq = at::empty({b}, X.options());
+    at::Tensor dX = backward ? at::empty_like(X) : at::Tensor();
+    if (b == 0) return {acq, dX};
+    auto work = scratch(evr_qparego_workspace_doubles(&stm, &g, &md, (int)b, backward), X);
+    check(evr_qparego_eval(s, &stm, &g, &md, &pg, (int)b, X.data_ptr<double>(), nullptr, work.data_ptr<double>(),
+                           acq.data_ptr<double>(), backward ? dX.data_ptr<double>() : nullptr),
+          "qparego_eval");
+    ++n_evals;
+    return {acq, dX};
+  }
+
+  int64_t evals() const { return n_evals; }
+};
+
+using ParegoPtr = c10::intrusive_ptr<QparegoAcq>;
+
+at::Tensor qparego_forward(const ParegoPtr& acq, const at::Tensor& X) { return std::get<0>(acq->eval(X, false)); }
+
+std::tuple<at::Tensor, at::Tensor> qparego_forward_backward(const ParegoPtr& acq, const at::Tensor& X) {
+  return acq->eval(X, true);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(everest_amd, m) {
+  m.class_<QparegoAcq>("QparegoAcq")
+      .def(torch::init<at::Tensor, at::Tensor, bool, double, double, at::Tensor, double, at::Tensor, at::Tensor,
+                       std::vector<at::Tensor>>())
+      .def("set_samples", &QparegoAcq::set_samples)
+      .def("evals", &QparegoAcq::evals);
   m.class_<QsoboAcq>("QsoboAcq")
       .def(torch::init<at::Tensor, at::Tensor, bool, double, double, at::Tensor, at::Tensor, at::Tensor,
                        std::vector<at::Tensor>>())
@@ -509,6 +623,8 @@ TORCH_LIBRARY(everest_amd, m) {
   m.def("qnei_backward(__torch__.torch.classes.everest_amd.QneiAcq acq, Tensor X, Tensor grad_out) -> Tensor");
   m.def("qsobo_forward(__torch__.torch.classes.everest_amd.QsoboAcq acq, Tensor X) -> Tensor");
   m.def("qsobo_forward_backward(__torch__.torch.classes.everest_amd.QsoboAcq acq, Tensor X) -> (Tensor, Tensor)");
+  m.def("qparego_forward(__torch__.torch.classes.everest_amd.QparegoAcq acq, Tensor X) -> Tensor");
+  m.def("qparego_forward_backward(__torch__.torch.classes.everest_amd.QparegoAcq acq, Tensor X) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(everest_amd, CUDA, m) {
@@ -524,4 +640,6 @@ TORCH_LIBRARY_IMPL(everest_amd, CUDA, m) {
   m.impl("qnei_backward", &qnei_backward);
   m.impl("qsobo_forward", &qsobo_forward);
   m.impl("qsobo_forward_backward", &qsobo_forward_backward);
+  m.impl("qparego_forward", &qparego_forward);
+  m.impl("qparego_forward_backward", &qparego_forward_backward);
 }

@@ -4,6 +4,6 @@ from .domain import (BaseModel, CategoricalInput, CloseToTargetObjective, Constr
                      MinimizeSigmoidObjective, MovingMaximizeSigmoidObjective, Outputs, TargetObjective)
 from .models import (AdditiveSoboStrategy, AnyStrategy, BotorchSurrogates, CategoricalEncodingEnum, CategoricalMethodEnum,
                      DimensionalityScaledLogNormalPrior, GammaPrior, LogNormalPrior, MaternKernel, NormalPrior,
-                     QehviStrategy, QnehviStrategy, RandomStrategy, RBFKernel, ScalerEnum, SingleTaskGPSurrogate,
+                     QehviStrategy, QnehviStrategy, QparegoStrategy, RandomStrategy, RBFKernel, ScalerEnum, SingleTaskGPSurrogate,
                      SoboStrategy, MoboStrategy, qEHVI, qEI, qLogEHVI, qLogEI, qLogNEHVI, qLogNEI, qNEHVI,
                      qNEI)

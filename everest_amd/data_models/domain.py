@@ -556,6 +556,14 @@ class Outputs(_Features):
         objectives see as x_adapt)."""
         return self.preprocess_experiments_all_valid_outputs(experiments, [output_feature_key])
 
+    def preprocess_experiments_any_valid_output(self, experiments: pd.DataFrame) -> pd.DataFrame:
+        """bofire/data_models/domain/features.py:976-1003: the rows where at least one output has
+        a valid (valid_<key> > 0), non-NaN observation."""
+        keep = np.zeros(len(experiments), dtype=bool)
+        for k in self.get_keys():
+            keep |= np.asarray(experiments[f"valid_{k}"] > 0, dtype=bool) & experiments[k].notna().to_numpy()
+        return experiments[keep]
+
     def validate_experiments(self, experiments: pd.DataFrame) -> pd.DataFrame:
         for feat in self.features:
             if feat.key not in experiments:

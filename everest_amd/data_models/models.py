@@ -387,6 +387,18 @@ class MoboStrategy(MultiobjectiveStrategy):
         return self
 
 
+class QparegoStrategy(MultiobjectiveStrategy):
+    """bofire/data_models/strategies/predictives/qparego.py:27-67."""
+    type: Literal["QparegoStrategy"] = "QparegoStrategy"
+    acquisition_function: AnySingleObjectiveAcquisitionFunction = Field(default_factory=qNEI)
+
+    @field_validator("domain")
+    @classmethod
+    def _objectives(cls, v):
+        """bofire/data_models/strategies/predictives/qparego.py:37-48."""
+        return _check_objectives(cls, v, _MO_CONSTRAINED)
+
+
 class SoboStrategy(BotorchStrategy):
     """bofire/data_models/strategies/predictives/sobo.py:15-62."""
     type: Literal["SoboStrategy"] = "SoboStrategy"
@@ -423,6 +435,6 @@ class AdditiveSoboStrategy(BotorchStrategy):
         return v
 
 
-AnyStrategy = Annotated[Union[QnehviStrategy, QehviStrategy, MoboStrategy, SoboStrategy, AdditiveSoboStrategy,
-                              RandomStrategy],
+AnyStrategy = Annotated[Union[QnehviStrategy, QehviStrategy, MoboStrategy, QparegoStrategy, SoboStrategy,
+                              AdditiveSoboStrategy, RandomStrategy],
                         Field(discriminator="type")]

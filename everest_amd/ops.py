@@ -654,6 +654,10 @@ def sobo_scan(Y: torch.Tensor, q: int, best: torch.Tensor, spec: SoboSpec, log: 
     """Scalarised, constraint-weighted scan alone (evr_sobo_scan): Y S x m_model x (b*q) joint
     samples (point i of candidate c at column c*q + i), best S incumbents or one ->
     (acq (b), dY like Y | None).  flags: m_model x b."""
+    return _utility_scan("evr_sobo_scan", Y, q, best, spec, log, tau_relu, tau_max, flags, gout, backward)
+
+
+def _utility_scan(symbol: str, Y, q, best, spec, log, tau_relu, tau_max, flags, gout, backward):
     Y, best = _dev(Y, "Y"), _dev(best, "best")
     S, m, bq = Y.shape
     q = int(q)
@@ -671,7 +675,7 @@ def sobo_scan(Y: torch.Tensor, q: int, best: torch.Tensor, spec: SoboSpec, log: 
     acq = torch.empty(b, dtype=torch.float64, device=Y.device)
     dY = torch.empty_like(Y) if backward else None
     sb = spec.struct(log, tau_relu, tau_max, best)
-    call("evr_sobo_scan", _stream(), q, m, S, b, ctypes.byref(sb), Y.data_ptr(), _p(flags), _p(gout),
+    call(symbol, _stream(), q, m, S, b, ctypes.byref(sb), Y.data_ptr(), _p(flags), _p(gout),
          acq.data_ptr(), _p(dY))
     return acq, dY
 
@@ -680,6 +684,10 @@ def qsobo_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviMo
                X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
     """Constrained / scalarised qNEI, qLogNEI, qLogEI, qEI over m model outputs (evr_qsobo_eval):
     X (b*q) x d raw candidates -> acq (b) [, dX (b*q) x d]."""
+    return _utility_eval("evr_qsobo", stm, g, model, sb, X, backward, gout)
+
+
+def _utility_eval(prefix: str, stm, g, model, sb, X, backward, gout):
     X = _dev(X, "X")
     q = int(g.q)
     bq, d = X.shape
@@ -687,13 +695,98 @@ def qsobo_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviMo
         raise ValueError(f"{bq} rows are not a multiple of q = {q}")
     b = bq // q
     lib = _native.load()
-    work = _workspace(lib.evr_qsobo_workspace_doubles(ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), b,
-                                                      int(backward)), X.device)
+    work = _workspace(getattr(lib, prefix + "_workspace_doubles")(ctypes.byref(stm), ctypes.byref(g),
+                                                                  ctypes.byref(model), b, int(backward)), X.device)
     acq = torch.empty(b, dtype=torch.float64, device=X.device)
     dX = torch.empty_like(X) if backward else None
-    call("evr_qsobo_eval", _stream(), ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), ctypes.byref(sb), b,
+    call(prefix + "_eval", _stream(), ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), ctypes.byref(sb), b,
          X.data_ptr(), _p(None if gout is None else _dev(gout, "gout")), work.data_ptr(), acq.data_ptr(), _p(dX))
     return acq, dX
+
+
+class ParegoSpec:
+    """Augmented Chebyshev utility over model outputs with output constraints for the qParEGO scan
+    (parego_scan.hip, evr_parego): t_k(y) = A_k g_k(y[out_k]) + B_k,
+    u(y) = min_k t_k(y) + alpha sum_k t_k(y).
+
+    terms: [(output, kind, p0, p1, A, B)] — OBJ_AFFINE p0*y + p1 or OBJ_CLOSE_TO_TARGET
+    -|y - p0|^p1, A > 0.  constraints: [(output, sign, threshold, eta)] as in ``SoboSpec``, whose
+    interface this class has (struct / utility / feasible)."""
+
+    def __init__(self, m_model: int, terms, alpha: float, constraints=()):
+        self.m_model = int(m_model)
+        self.alpha = float(alpha)
+        self.terms = [(int(o), int(k), float(p0), float(p1), float(A), float(B)) for o, k, p0, p1, A, B in terms]
+        self.constraints = [(int(o), float(sg), float(t), float(e)) for o, sg, t, e in constraints]
+        if not 2 <= len(self.terms) <= 8 or len(self.constraints) > 16:
+            raise ValueError("parego scan: 2..8 terms and at most 16 output constraints")
+        if not self.alpha >= 0.0:
+            raise ValueError(f"parego scan: alpha = {self.alpha} is negative")
+        for o, *_ in self.terms + self.constraints:
+            if not 0 <= o < self.m_model:
+                raise ValueError(f"parego scan: output index {o} outside the model's {self.m_model} outputs")
+        for _, k, _, _, A, _ in self.terms:
+            if k not in (OBJ_AFFINE, OBJ_CLOSE_TO_TARGET):
+                raise ValueError(f"parego scan: term kind {k}")
+            if not A > 0.0:
+                raise ValueError(f"parego scan: term scale A = {A} must be positive")
+        tm = self.terms
+        self._tarrs = (np.array([t[0] for t in tm], np.int32), np.array([t[1] for t in tm], np.int32)) + tuple(
+            np.array([t[i] for t in tm], np.float64) for i in (2, 3, 4, 5))
+        cs = self.constraints or [(0, 0.0, 0.0, 1.0)]
+        self._carrs = (np.array([c[0] for c in cs], np.int32), np.array([c[1] for c in cs], np.float64),
+                       np.array([c[2] for c in cs], np.float64), np.array([c[3] for c in cs], np.float64))
+
+    def struct(self, log: bool, tau_relu: float, tau_max: float, best: torch.Tensor) -> "_native.EvrParego":
+        """evr_parego over ``best`` (device; S per-sample incumbents, or one value: stride 0).  The
+        struct points into this spec's host arrays and into ``best``: keep both alive."""
+        best = _dev(best, "best")
+        pg = _native.EvrParego()
+        pg.log, pg.tau_relu, pg.tau_max = int(bool(log)), float(tau_relu), float(tau_max)
+        pg.best, pg.best_stride = best.data_ptr(), 0 if best.numel() == 1 else 1
+        pg.alpha = self.alpha
+        pg.n_term, pg.n_con = len(self.terms), len(self.constraints)
+        (pg.term_out, pg.term_kind, pg.term_p0, pg.term_p1, pg.term_a,
+         pg.term_b) = (a.ctypes.data for a in self._tarrs)
+        pg.con_out, pg.con_sign, pg.con_thr, pg.con_eta = (a.ctypes.data for a in self._carrs)
+        return pg
+
+    def term_values(self, Y):
+        """The terms t_k of model-output rows Y (... x m_model), stacked on a new last axis."""
+        xp = torch if isinstance(Y, torch.Tensor) else np
+        return xp.stack([A * SoboSpec._term(k, p0, p1, 0.0, Y[..., o]) + B for o, k, p0, p1, A, B in self.terms], -1)
+
+    def utility(self, Y):
+        """u of model-output rows Y (... x m_model; numpy array or torch tensor)."""
+        t = self.term_values(Y)
+        mn = t.min(-1)
+        if isinstance(Y, torch.Tensor):
+            mn = mn.values
+        return mn + self.alpha * t.sum(-1)
+
+    def term_slopes(self, Y) -> np.ndarray:
+        """d u / d t_k of model-output rows Y (numpy, ... x m_model) as the scan's backward takes
+        it: alpha + [k == k*], k* the FIRST arg-min (the lowest term index on ties)."""
+        t = self.term_values(np.asarray(Y, dtype=np.float64))
+        first = np.argmin(t, axis=-1)               # numpy: the first occurrence of the minimum
+        return self.alpha + (np.arange(t.shape[-1]) == first[..., None])
+
+    feasible = SoboSpec.feasible
+
+
+def parego_scan(Y: torch.Tensor, q: int, best: torch.Tensor, spec: ParegoSpec, log: bool = False,
+                tau_relu: float = 1e-6, tau_max: float = 1e-2, flags: Optional[torch.Tensor] = None,
+                gout: Optional[torch.Tensor] = None, backward: bool = False):
+    """Augmented Chebyshev, constraint-weighted scan alone (evr_parego_scan); arguments and results
+    as ``sobo_scan``."""
+    return _utility_scan("evr_parego_scan", Y, q, best, spec, log, tau_relu, tau_max, flags, gout, backward)
+
+
+def qparego_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviModel", pg: "_native.EvrParego",
+                 X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
+    """qParEGO's qNEI, qLogNEI, qLogEI, qEI over m model outputs (evr_qparego_eval):
+    X (b*q) x d raw candidates -> acq (b) [, dX (b*q) x d]."""
+    return _utility_eval("evr_qparego", stm, g, model, pg, X, backward, gout)
 
 
 class QnehviPlan:

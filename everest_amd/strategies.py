@@ -1,6 +1,6 @@
 """Functional strategies with BoFire's API — ``map(data_model)`` returns an object with
 ``tell / ask / predict / calc_acquisition`` (bofire/strategies/{strategy,random}.py,
-bofire/strategies/predictives/{predictive,botorch,qehvi,qnehvi,sobo}.py).
+bofire/strategies/predictives/{predictive,botorch,qehvi,qnehvi,sobo,qparego}.py).
 
 The dense work (GP fit and posterior, qNEHVI / qEI construction and evaluation) runs on the
 MI355X through ``everest_amd.gp`` / ``everest_amd.acquisition``; the orchestration (pandas,
@@ -20,8 +20,8 @@ import torch
 
 from . import data_models as dm
 from . import ops
-from .acquisition import (QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI, QSoboLogEI,
-                          QSoboLogNEI, QSoboNEI, prefetch_scramble)
+from .acquisition import (QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI, QParegoLogEI,
+                          QParegoLogNEI, QParegoNEI, QSoboLogEI, QSoboLogNEI, QSoboNEI, prefetch_scramble)
 from .data_models.domain import CloseToTargetObjective, MaximizeObjective, MinimizeObjective
 from .optim import (OptimizeStats, hit_and_run, host_values, optimize_acqf, optimize_acqf_mixed,
                     prefetch_raw_samples)
@@ -873,10 +873,203 @@ class AdditiveSoboStrategy(SoboStrategy):
     _additive = True
 
 
+PAREGO_ALPHA = 0.05      # [upstream] get_chebyshev_scalarization(alpha=0.05)
+MAX_JOINT_Q = 12         # EVR_QNG_MAX_Q: the largest joint batch (new + pending points) of the device chain
+
+
+def sample_simplex_weights(k: int, gen: torch.Generator) -> np.ndarray:
+    """One uniform draw from the (k-1)-simplex — [upstream] botorch.utils.sampling.sample_simplex
+    (restated from memory, parity-unpinned): k - 1 sorted uniforms, the weights are the
+    differences of [0, r, 1]."""
+    r = torch.sort(torch.rand(k - 1, dtype=torch.float64, generator=gen)).values
+    edges = torch.cat([torch.zeros(1, dtype=torch.float64), r, torch.ones(1, dtype=torch.float64)])
+    return (edges[1:] - edges[:-1]).numpy()
+
+
+def chebyshev_terms(weights, mask, z, keys: Sequence[str]):
+    """(A_k, B_k) of the device utility u = min_k t_k + alpha sum_k t_k, t_k = A_k g_k + B_k —
+    [upstream] get_chebyshev_scalarization(weights = w * mask, Y = z) applied to g * mask
+    (restated from memory of BoTorch, parity-unpinned): z (rows x K, already masked) gives the
+    normalisation bounds lo / hi (column min / max; one row: hi = lo + 1); columns with a
+    negative scalarisation weight (mask = -1) are shifted to [-1, 0], and the negated
+    max-plus-sum of the negated products is min_k t_k + alpha sum_k t_k with
+
+        mask = +1:  t_k = w_k (g_k - lo_k) / (hi_k - lo_k)
+        mask = -1:  t_k = w_k (hi_k + g_k) / (hi_k - lo_k)      (= w_k (1 - z_hat_k), z = -g).
+
+    Deviation: hi_k == lo_k raises ValueError naming the output (upstream divides by zero), and
+    so does a weight that is not positive (a zero weight has no sign to pick the branch by)."""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    mask = np.asarray(mask, dtype=np.float64).reshape(-1)
+    z = np.asarray(z, dtype=np.float64).reshape(-1, len(w))
+    if z.shape[0] == 0:
+        raise ValueError("qParEGO needs at least one experiment with a valid output")
+    lo = z.min(axis=0)
+    hi = lo + 1.0 if z.shape[0] == 1 else z.max(axis=0)
+    out = []
+    for k, key in enumerate(keys):
+        if not w[k] > 0.0:
+            raise ValueError(f"qParEGO weight {w[k]} of output `{key}` is not positive")
+        if hi[k] == lo[k]:
+            raise ValueError(f"output `{key}`: the predicted objective values span a zero range; the Chebyshev "
+                             "scalarisation cannot normalise it")
+        A, l, h = float(w[k] / (hi[k] - lo[k])), float(lo[k]), float(hi[k])
+        out.append((A, -A * l) if mask[k] > 0 else (A, A * h))
+    return out
+
+
+class QparegoStrategy(BotorchStrategy):
+    """bofire/strategies/predictives/qparego.py:30-140 — qParEGO: one random augmented Chebyshev
+    scalarisation of the Maximize / Minimize / CloseToTarget objectives per ask, and one q = 1
+    acquisition (qNEI, the data model's default, qLogNEI, qLogEI or qEI) per candidate, optimised
+    one after the other.  Runs QParegoNEI / QParegoLogNEI / QParegoLogEI over all model outputs
+    (parego_scan.hip).
+
+    Restated from memory of BoTorch (not importable here, so parity-unpinned): sample_simplex
+    (``sample_simplex_weights``), get_chebyshev_scalarization (``chebyshev_terms``) and
+    optimize_acqf_list — candidate i is optimised on acquisition i with the i candidates chosen
+    so far as its pending points (set_X_pending; qparego.py:132 gives the strategy's own pending
+    candidates to acquisition 0 only).
+
+    Seed order: the weights first (one draw of K - 1 uniforms from ``self.gen``; none when
+    ``weights`` is given), then every acquisition's seeds in order — prune seed (when pruning)
+    and sampler seed for the NEI kinds, one seed for the EI kinds — all before the first
+    optimiser draw, as the reference builds the whole list before optimising.  Acquisition i is
+    built from its pre-drawn seeds once candidate i - 1 is known.
+
+    Deviations: the NEI kinds follow ``acquisition_function.prune_baseline`` (the reference
+    passes prune_baseline=True whatever the data model says; the default is True); a zero
+    normalisation range raises (``chebyshev_terms``)."""
+
+    def __init__(self, data_model, dist=None, weights=None, **kwargs):
+        super().__init__(data_model, dist=dist)
+        self.acquisition_function = data_model.acquisition_function
+        self.weights = weights          # optional hook: fixed simplex weights instead of the draw
+        self.last_weights = None
+        self.last_acqf = None
+        self.last_acqfs: list = []
+
+    def _draw_seed(self) -> int:
+        return int(torch.randint(0, 1000000, (1,), generator=self.gen).item())
+
+    def _parego_spec(self) -> ops.ParegoSpec:
+        """_get_objective_and_constraints (qparego.py:40-110) as the device scan's table."""
+        assert self.experiments is not None, "No experiments available."
+        outputs = self.domain.outputs
+        kinds = [MaximizeObjective, MinimizeObjective, CloseToTargetObjective]
+        keys = outputs.get_keys_by_objective(kinds)
+        mask = get_ref_point_mask(self.domain)
+        if self.weights is None:
+            w = sample_simplex_weights(len(keys), self.gen)
+        else:
+            w = np.asarray(self.weights, dtype=np.float64).reshape(-1)
+            if len(w) != len(keys):
+                raise ValueError(f"weights: expected {len(keys)} values, got {len(w)}")
+        self.last_weights = w
+        preds = self.predict(outputs.preprocess_experiments_any_valid_output(self.experiments))
+        z = np.stack([mask[k] * np.asarray(outputs.get_by_key(key).objective(preds[f"{key}_pred"].to_numpy()),
+                                           dtype=np.float64) for k, key in enumerate(keys)], axis=-1)
+        ab = chebyshev_terms(w, mask, z, keys)
+        mkeys = list(self.model.output_keys)
+        terms = [objective_term(outputs.get_by_key(key).objective, mkeys.index(key)) + ab[k]
+                 for k, key in enumerate(keys)]
+        constraints = []
+        if len(keys) != len(outputs.get_by_objective(dm.domain.Objective).features):     # qparego.py:98-104
+            constraints = get_output_constraints(outputs, self.experiments, mkeys)
+        return ops.ParegoSpec(len(mkeys), terms, PAREGO_ALPHA, constraints)
+
+    def _acqf_kind(self):
+        af = self.acquisition_function
+        if not isinstance(af, (dm.qEI, dm.qLogEI, dm.qNEI, dm.qLogNEI)):
+            raise NotImplementedError(f"{type(af).__name__} is out of scope; use qNEI(), qLogNEI(), qLogEI() or qEI()")
+        return af
+
+    def _draw_acqf_seeds(self):
+        af = self._acqf_kind()
+        if isinstance(af, (dm.qNEI, dm.qLogNEI)):
+            prune_seed = self._draw_seed() if af.prune_baseline else 0
+            return (prune_seed, self._draw_seed())
+        return (self._draw_seed(),)
+
+    def _build_acqf(self, spec: ops.ParegoSpec, seeds, X_train, X_pending):
+        af = self._acqf_kind()
+        S = int(af.n_mc_samples)
+        npend = 0 if X_pending is None else len(X_pending)
+        if 1 + npend > MAX_JOINT_Q:
+            raise ValueError(f"qParEGO: a joint batch of 1 new and {npend} pending points exceeds the device "
+                             f"chain's limit of {MAX_JOINT_Q} (EVR_QNG_MAX_Q)")
+        if isinstance(af, (dm.qNEI, dm.qLogNEI)):
+            cls = QParegoLogNEI if isinstance(af, dm.qLogNEI) else QParegoNEI
+            acqf = cls(self.model, self.model.X_raw, X_train, spec, S=S, sampler_seed=seeds[1],
+                       prune_baseline=af.prune_baseline, prune_seed=seeds[0], X_pending_raw=X_pending)
+        else:
+            acqf = QParegoLogEI(self.model, X_train, spec, S=S, seed=seeds[0], X_pending_raw=X_pending,
+                                log=isinstance(af, dm.qLogEI))
+        self.last_acqf = acqf
+        return acqf
+
+    def _get_acqfs(self, n):
+        """_get_acqfs (qparego.py:112-140): n acquisitions over one scalarisation; only the first
+        carries the strategy's pending candidates."""
+        X_train, X_pending = self.get_acqf_input_tensors()
+        spec = self._parego_spec()
+        seeds = [self._draw_acqf_seeds() for _ in range(n)]
+        return [self._build_acqf(spec, seeds[i], X_train, X_pending if i == 0 else None) for i in range(n)]
+
+    def calc_acquisition(self, candidates: pd.DataFrame, combined: bool = False) -> np.ndarray:
+        """Values of acquisition 0 (a fresh scalarisation unless ``weights`` is set)."""
+        acqf = self._get_acqfs(1)[0]
+        X = torch.as_tensor(self._transform(candidates), dtype=torch.float64, device=self.model.device)
+        if combined:
+            X = X.unsqueeze(0)
+        return host_values(acqf.forward(X))
+
+    def _ask(self, candidate_count: Optional[int] = None) -> pd.DataFrame:
+        """optimize_acqf_list over the acquisition list: round i optimises acquisition i (q = 1)
+        with the i earlier winners as pending points."""
+        q = 1 if candidate_count is None else int(candidate_count)
+        assert q > 0, "candidate_count has to be larger than zero."
+        if self.experiments is None:
+            raise ValueError("No experiments have been provided yet.")
+        X_train, X_pending = self.get_acqf_input_tensors()
+        npend = 0 if X_pending is None else len(X_pending)
+        if q > MAX_JOINT_Q or 1 + npend > MAX_JOINT_Q:
+            raise ValueError(f"qParEGO: {q} candidates with {npend} pending points need a joint batch above the "
+                             f"device chain's limit of {MAX_JOINT_Q} (EVR_QNG_MAX_Q); candidate_count <= "
+                             f"{MAX_JOINT_Q}")
+        ineq = get_linear_constraints(self.domain, dm.LinearInequalityConstraint)
+        eq = get_linear_constraints(self.domain, dm.LinearEqualityConstraint)
+        combos = self.get_categorical_combinations()
+        spec = self._parego_spec()                                  # weights first
+        seeds = [self._draw_acqf_seeds() for _ in range(q)]         # then every acquisition's seeds
+        chosen, values, stats = [], [], None
+        self.last_acqfs = []
+        for i in range(q):
+            pend = [] if (i > 0 or X_pending is None) else [np.asarray(X_pending, dtype=np.float64)]
+            if chosen:
+                pend.append(np.stack(chosen))
+            acqf = self._build_acqf(spec, seeds[i], X_train, np.concatenate(pend, 0) if pend else None)
+            self.last_acqfs.append(acqf)
+            if len(combos) > 1:     # EXHAUSTIVE categorical method: optimize_acqf_mixed
+                x, v, stats = optimize_acqf_mixed(acqf, self._bounds(), combos, self.num_restarts,
+                                                  self.num_raw_samples, self._get_optimizer_options(), self.gen, ineq,
+                                                  eq, dist=self.dist, q=1)
+            else:
+                x, v, stats = optimize_acqf(acqf, self._bounds(), self.num_restarts, self.num_raw_samples,
+                                            self._get_optimizer_options(), self.gen, ineq, eq, dist=self.dist,
+                                            fixed_features=combos[0] or None, q=1)
+            chosen.append(np.asarray(x, dtype=np.float64).reshape(-1))
+            values.append(v)
+        stats.best_value = values
+        self.last_ask_stats = stats
+        return self._postprocess_candidates(np.stack(chosen))
+
+
 STRATEGY_MAP = {
     dm.QnehviStrategy: QnehviStrategy,
     dm.QehviStrategy: QehviStrategy,
     dm.MoboStrategy: MoboStrategy,
+    dm.QparegoStrategy: QparegoStrategy,
     dm.SoboStrategy: SoboStrategy,
     dm.AdditiveSoboStrategy: AdditiveSoboStrategy,
     dm.RandomStrategy: RandomStrategy,

@@ -15,6 +15,8 @@ AcquisitionFunction.forward protocols called at bofire/strategies/predictives/bo
     torch.ops.everest_amd.qnei_forward / qnei_forward_backward / qnei_backward   (qNEI, qLogNEI, qLogEI)
     torch.classes.everest_amd.QsoboAcq(state, model, log, tau_relu, tau_max, best, terms, constraints, keep)
     torch.ops.everest_amd.qsobo_forward / qsobo_forward_backward   (scalarised / output-constrained SOBO)
+    torch.classes.everest_amd.QparegoAcq(state, model, log, tau_relu, tau_max, best, alpha, terms, constraints, keep)
+    torch.ops.everest_amd.qparego_forward / qparego_forward_backward   (qParEGO: augmented Chebyshev utility)
 
 No fallback: a missing library raises NativeLibraryError."""
 from __future__ import annotations
@@ -102,6 +104,26 @@ class QsoboFunction(torch.autograd.Function):
             return a
         ctx.save_for_backward(None)
         return ops.qsobo_forward(acq, X)
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        (dX,) = ctx.saved_tensors
+        return dX * grad_out.reshape(-1, 1, 1), None
+
+
+class QparegoFunction(torch.autograd.Function):
+    """acq = QParegoNEI / QParegoLogNEI / QParegoLogEI(X), X b x q x d, through
+    torch.ops.everest_amd.qparego_* on a torch.classes.everest_amd.QparegoAcq; as QneiFunction."""
+
+    @staticmethod
+    def forward(ctx, X: torch.Tensor, acq):
+        ops = load()
+        if ctx.needs_input_grad[0]:
+            a, dX = ops.qparego_forward_backward(acq, X)
+            ctx.save_for_backward(dX)
+            return a
+        ctx.save_for_backward(None)
+        return ops.qparego_forward(acq, X)
 
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):

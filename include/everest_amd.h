@@ -523,6 +523,51 @@ int evr_qsobo_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_gener
                    const evr_sobo* sb, int b, const double* X, const double* gout, double* work, double* acq,
                    double* dX);
 
+/* ---- augmented Chebyshev scalarisation scan with output constraints (parego_scan.hip) ------
+ * The step between the joint samples Y of q-point candidates and dY for the qParEGO utility
+ * over several model outputs (2..EVR_SOBO_MAX_TERMS terms),
+ *   t_k(y) = A_k * g_k(y[out_k]) + B_k,   u(y) = min_k t_k(y) + alpha * sum_k t_k(y),
+ * ([upstream] get_chebyshev_scalarization as reached from BoFire's QparegoStrategy,
+ * bofire/strategies/predictives/qparego.py:30-140; weights, normalisation bounds and signs are
+ * folded into A_k > 0 and B_k by the caller) and 0..16 output constraints as in evr_sobo_scan.
+ * The reductions over the q points and the samples, Y / dY, flags, best / best_stride, gout and
+ * the plain-mode subgradients are exactly those of evr_sobo_scan.  Term kinds: EVR_OBJ_AFFINE
+ * (p0*y + p1) and EVR_OBJ_CLOSE_TO_TARGET (-|y - p0|^p1) only.  Backward: the slope of u with
+ * respect to t_k is alpha + [k == k*], k* the FIRST arg-min (lowest term index on ties); dY is
+ * written in full, outputs nothing reads get exact zeros.  The term / constraint arrays are HOST
+ * arrays (copied into the launch); best is on the device.  Refused: n_term < 2, any other term
+ * kind, A_k <= 0, alpha < 0, eta <= 0, an output index outside the model.  Forward and backward
+ * are ONE launch; no atomics; results are bitwise reproducible. */
+typedef struct {
+  int log;                  /* 0: plain (qNEI / qEI), 1: log (qLogNEI / qLogEI) */
+  double tau_relu;          /* log mode: fatplus temperature */
+  double tau_max;           /* log mode: fatmax temperature */
+  const double* best;       /* device: incumbent(s) in utility space */
+  int best_stride;          /* 1: S per-sample values, 0: one value */
+  double alpha;             /* augmentation weight (>= 0; [upstream] 0.05) */
+  int n_term;               /* 2..EVR_SOBO_MAX_TERMS */
+  const int* term_out;      /* n_term: model output index */
+  const int* term_kind;     /* n_term: EVR_OBJ_AFFINE or EVR_OBJ_CLOSE_TO_TARGET */
+  const double* term_p0;
+  const double* term_p1;
+  const double* term_a;     /* n_term: scale A_k > 0 */
+  const double* term_b;     /* n_term: shift B_k */
+  int n_con;                /* 0..16 */
+  const int* con_out;
+  const double* con_sign;
+  const double* con_thr;
+  const double* con_eta;
+} evr_parego;
+int evr_parego_scan(void* stream, int q, int m_model, int S, int b, const evr_parego* pg, const double* Y,
+                    const int* flags, const double* gout, double* acq, double* dY);
+/* Full evaluation: evr_qsobo_eval's chain (same stm / g / md / X / work / acq / dX semantics)
+ * with evr_parego_scan in place of evr_sobo_scan. */
+long long evr_qparego_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                        const evr_qnehvi_model* md, int b, int backward);
+int evr_qparego_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                     const evr_parego* pg, int b, const double* X, const double* gout, double* work, double* acq,
+                     double* dX);
+
 /* The PyTorch-ROCm operators torch.ops.everest_amd.qnehvi_*(everest_amd/csrc/torch_ops.cpp)
  * take a torch.classes.everest_amd.QnehviAcq: it copies the evr_qnehvi_state /
  * evr_qnehvi_model / evr_qn_general structs, holds references to the device tensors they
