@@ -156,8 +156,9 @@ __global__ void mll_copy_in(int B, int n, int d, const double* hx, const double*
 __global__ void mll_copy_out(int B, int d, int nch, const double* __restrict__ part, const double* __restrict__ gls,
                              const int* __restrict__ info, const double* hx, double* hout) {
   const int t = threadIdx.x;
-  if (t < B * 5) {
-    const int b = t / 5, q = t - b * 5;
+  // one block: every loop strides over blockDim, so any B works (B >= 52 has more than 256 terms)
+  for (int e = t; e < B * 5; e += blockDim.x) {
+    const int b = e / 5, q = e - b * 5;
     double s = 0.0;
     // the chunk partials' loads in flight together (clamped indices), summed in chunk order
     for (int c0 = 0; c0 < nch; c0 += 32) {
@@ -168,10 +169,10 @@ __global__ void mll_copy_out(int B, int d, int nch, const double* __restrict__ p
       for (int u = 0; u < 32; ++u)
         if (c0 + u < nch) s += v[u];
     }
-    hout[t] = q == 0 ? 2.0 * s : s;
+    hout[e] = q == 0 ? 2.0 * s : s;
   }
   for (int i = t; i < B * d; i += blockDim.x) hout[B * 5 + i] = gls[i];
-  if (t < B) hout[B * 5 + B * d + t] = (double)info[t];
+  for (int i = t; i < B; i += blockDim.x) hout[B * 5 + B * d + i] = (double)info[i];
   __threadfence_system();
   __syncthreads();
   if (t == 0) {

@@ -32,6 +32,48 @@ def test_posterior_parity(kind, n, d, m):
             assert torch.allclose(var[j].cpu(), rv, rtol=1e-7, atol=1e-10 * ost[j].y_std ** 2)
 
 
+def _post_workgroups(n, nt, B):
+    """Workgroups of the 32 x 64-tile posterior projection (evr_gp_posterior's switch: PostCfgW
+    from 1024 on, else 32 x 32 tiles)."""
+    return -(-nt // 64) * -(-n // 32) * B
+
+
+@pytest.mark.parametrize("n,d,m,nt,wide", [(257, 6, 4, 1857, True),    # PostCfgW, n and nt odd: scalar loads
+                                           (130, 16, 8, 1664, True),   # PostCfgW, paired loads; d = 16: MFMA K_*,
+                                                                       # the arrival counters zeroed by the memset
+                                           (130, 16, 1, 95, False)])   # PostCfg, scalar loads, d >= 16
+def test_posterior_projection_dispatch(n, d, m, nt, wide):
+    """post_proj_kernel on either side of its 1024-workgroup switch against the oracle, with the
+    bars of test_posterior_parity; 8 test points sit on training rows; a second call is bitwise equal
+    (the arrival counters are zeroed again, the last arrival sums in a fixed order)."""
+    count = _post_workgroups(n, nt, m)
+    assert (count >= 1024) == wide, f"{count} workgroups: the case moved to the other kernel"
+    X, Y, lo, hi, hyp = make_problem(n=n, d=d, m=m, seed=n + d + nt, lo=-np.ones(d), hi=2 * np.ones(d))
+    ost = oracle_states(X, Y, lo, hi, hyp)
+    gp = device_gp(X, Y, lo, hi, hyp)
+    rng = np.random.default_rng(2)
+    Xs = lo + (hi - lo) * rng.uniform(size=(nt, d))
+    rows = rng.choice(n, 8, replace=False)
+    Xs[rng.choice(nt, 8, replace=False)] = X[rows]
+    Xd = torch.tensor(Xs, device="cuda")
+    Xo = torch.tensor((Xs - lo) / (hi - lo))
+    for obs in (False, True):
+        mean, var = gp.posterior(Xd, observation_noise=obs)
+        mean2, var2 = gp.posterior(Xd, observation_noise=obs)
+        torch.cuda.synchronize()
+        assert torch.equal(mean, mean2) and torch.equal(var, var2)
+        refs = [ogp.posterior(ost[j], Xo, observation_noise=obs) for j in range(m)]
+        em = max(float(((mean[j].cpu() - rm).abs() / (1e-9 * ost[j].y_std + 1e-9 * rm.abs())).max())
+                 for j, (rm, _) in enumerate(refs))
+        ev = max(float(((var[j].cpu() - rv).abs() / (1e-10 * ost[j].y_std ** 2 + 1e-7 * rv.abs())).max())
+                 for j, (_, rv) in enumerate(refs))
+        print(f"posterior n={n} d={d} m={m} nt={nt} obs={obs}: mean error / bar {em:.3e}, "
+              f"variance error / bar {ev:.3e}")
+        for j, (rm, rv) in enumerate(refs):
+            assert torch.allclose(mean[j].cpu(), rm, rtol=1e-9, atol=1e-9 * ost[j].y_std)
+            assert torch.allclose(var[j].cpu(), rv, rtol=1e-7, atol=1e-10 * ost[j].y_std ** 2)
+
+
 def test_config2_posterior_1024_sobol_points():
     """BASELINE configs[1]: SingleTaskGP RBF, n_train = 256, d = 6,
     X_train ~ U[0,1]^6 (default_rng(0)), y = DTLZ2(6, 5)'s first objective; hyperparameters
