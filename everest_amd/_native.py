@@ -203,6 +203,7 @@ _SIGS = {
                                        c_int, c_int], c_longlong),
     "evr_qparego_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
                           POINTER(EvrParego), c_int] + [c_void_p] * 5, c_int),
+    "evr_nipv_reduce": ([c_void_p] + [c_int] * 7 + [c_void_p] * 2 + [c_int] + [c_void_p] * 13, c_int),
     "evr_objective_general": ([c_void_p, c_int, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 4, c_int),
     "evr_objective_weights": ([c_void_p, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 3, c_int),
     "evr_cells_kd_limits": ([c_int, c_int, c_int, c_void_p], c_int),

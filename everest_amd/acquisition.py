@@ -1554,3 +1554,117 @@ class QEI:
         dK = ops.gemm(gp.M, gR.unsqueeze(0), transA=True)      # 1 x n x b
         dX = ops.kernel_cross_grad(gp.Xn, X, gp.ls, dK, gp.kind, shift2=gp.lo, scale2=gp.inv_range)
         return acq, dX
+
+
+class QNegIntPosVar:
+    """Device negative integrated posterior variance — [upstream]
+    qNegIntegratedPosteriorVariance with a ScalarizedPosteriorTransform over several outputs, as
+    ActiveLearningStrategy._get_acqfs builds it
+    (bofire/strategies/predictives/active_learning.py:16-66).  BoTorch is not importable here:
+    the semantics are restated from memory and parity-unpinned against it.
+
+    For a candidate X_c of q joint points (new points, then the pending points) the model is
+    conditioned on fantasy observations at X_c carrying the fitted noise — their values do not
+    enter, the variance does not depend on them — and the posterior variance of the scalarised
+    output sum_j w_j y_j is averaged over the N integration points P:
+
+        acq(X_c) = - sum_j coef_j (v0_j - tr(A_j^-1 G_j) / N),      coef_j = w_j^2 ys_j^2,
+        Vp_j = Linv_j k_j(Xn, P),   v0_j = mean_p (1 - |Vp_j[:, p]|^2),   Vx_j = Linv_j k_j(Xn, X_c),
+        C_j = k_j(P, X_c) - Vp_j^T Vx_j,   A_j = k_j(X_c, X_c) - Vx_j^T Vx_j + noise_j I,   G_j = C_j^T C_j
+
+    in standardised units (k_j(x, x) = 1, ys_j the standardisation scale).  Vp, v0 and coef are
+    computed once here; an evaluation is kernel assembly, two f64 GEMMs and the fused reduction
+    of nipv.hip (evr_nipv_reduce), its backward two more GEMMs and kernel_cross_grad.
+
+    ``P_raw`` (N x d) and ``X_pending_raw`` are raw (transformed, unnormalised) inputs like the
+    candidates; ``weights`` one w_j per model output (None: 1 for one output, 1 / B else).  A joint
+    batch above 12 points raises ValueError; outputs fitted on different row sets raise
+    NotImplementedError.  A candidate whose q x q block is not positive definite evaluates to NaN
+    (optim.host_values raises NotPSDError on every rank together)."""
+
+    log_acqf = False
+    supports_plan = False
+    nonnegative = False     # values are <= 0: optimize_acqf takes initialize_q_batch ([upstream] is_nonnegative)
+
+    def __init__(self, gp: GPBatch, P_raw, weights=None, X_pending_raw=None):
+        if gp.mask is not None:
+            raise NotImplementedError("QNegIntPosVar: outputs fitted on different row sets are not supported")
+        self.gp = gp
+        self.dev = gp.device
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        P = torch.as_tensor(np.asarray(P_raw, dtype=np.float64), **f64).reshape(-1, gp.d).contiguous()
+        if P.shape[0] < 1:
+            raise ValueError("QNegIntPosVar needs at least one integration point")
+        self.mc_points = P
+        self.N = int(P.shape[0])
+        if weights is None:
+            w = np.full(gp.B, 1.0 if gp.B == 1 else 1.0 / gp.B)
+        else:
+            w = np.asarray(weights, dtype=np.float64).reshape(-1)
+            if len(w) != gp.B:
+                raise ValueError(f"QNegIntPosVar: {len(w)} weights for {gp.B} outputs")
+        self.weights = w
+        self.coef = (torch.as_tensor(w, **f64) ** 2 * gp.ys ** 2).contiguous()
+        self.X_pending = None
+        if X_pending_raw is not None and np.asarray(X_pending_raw).shape[0] > 0:
+            self.X_pending = torch.as_tensor(np.asarray(X_pending_raw, dtype=np.float64).reshape(-1, gp.d), **f64)
+        self.n_pending = 0 if self.X_pending is None else int(self.X_pending.shape[0])
+        self._lo = gp.lo.to(**f64).contiguous()
+        self._ir = gp.inv_range.to(**f64).contiguous()
+        self.Pn = ((P - self._lo) * self._ir).contiguous()
+        self.Vp = ops.gemm(gp.Linv, ops.kernel_matrix(gp.Xn, self.Pn, gp.ls, gp.kind))     # B x n x N
+        self.v0 = (1.0 - (self.Vp * self.Vp).sum(dim=1).mean(dim=1)).contiguous()            # B
+
+    def _joint(self, X: torch.Tensor) -> torch.Tensor:
+        X = X.to(device=self.dev, dtype=torch.float64)
+        if X.dim() == 2:
+            X = X.unsqueeze(1)
+        if X.dim() != 3 or X.shape[-1] != self.gp.d:
+            raise ValueError(f"QNegIntPosVar: X must be b x d or b x q x {self.gp.d}, got {tuple(X.shape)}")
+        if self.X_pending is not None:
+            X = torch.cat([X, self.X_pending.unsqueeze(0).expand(X.shape[0], -1, -1)], dim=1)
+        if X.shape[1] > ops.QNG_MAX_Q:
+            raise ValueError(f"QNegIntPosVar: a joint batch of {X.shape[1]} points ({self.n_pending} pending) "
+                             f"exceeds the device kernel's limit of {ops.QNG_MAX_Q}")
+        return X.contiguous()
+
+    def _run(self, X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor]):
+        gp = self.gp
+        q_new = 1 if X.dim() == 2 else X.shape[1]
+        X3 = self._joint(X)
+        b, qq, d = X3.shape
+        if b == 0:
+            e = torch.empty(0, dtype=torch.float64, device=self.dev)
+            return e, (torch.empty(0, q_new, d, dtype=torch.float64, device=self.dev) if backward else None)
+        X2 = X3.view(b * qq, d)
+        R = ops.gemm(gp.M, gp.cross(X2))                                    # B x (n + 1) x bq; rows 0..n-1 = Vx
+        C = ops.kernel_matrix(self.Pn, X2, gp.ls, gp.kind, shift2=self._lo, scale2=self._ir)
+        n, N, B, bq = gp.n, self.N, gp.B, b * qq
+        # C -= Vp^T Vx on the rows 0..n-1 of R in place (batch stride (n + 1) bq, no copy)
+        _native.call("evr_gemm_f64", ops._stream(), 1, 0, N, bq, n, -1.0, self.Vp.data_ptr(), N, n * N,
+                     R.data_ptr(), bq, (n + 1) * bq, 1.0, C.data_ptr(), bq, N * bq, B)
+        acq, flags, dC, dVx, dXs = ops.nipv_reduce(C, R, X3, self._lo, self._ir, gp.ls, gp.kind, gp.noise, self.coef,
+                                                   self.v0, n=n, backward=backward, gout=gout)
+        # NaN marks a candidate whose q x q block was not p.d.; no host sync here —
+        # optim.host_values raises NotPSDError after the (all-)gather (as QEI._run does)
+        acq = torch.where(flags != 0, torch.full_like(acq, math.nan), acq)
+        if not backward:
+            return acq, None
+        ops.gemm(self.Vp, dC, alpha=-1.0, beta=1.0, out=dVx)               # dVx -= Vp dC
+        dKx = ops.gemm(gp.Linv, dVx, transA=True)                          # B x n x bq
+        dX = ops.kernel_cross_grad(gp.Xn, X2, gp.ls, dKx, gp.kind, shift2=self._lo, scale2=self._ir)
+        dX += ops.kernel_cross_grad(self.Pn, X2, gp.ls, dC, gp.kind, shift2=self._lo, scale2=self._ir)
+        dX = dX.view(b, qq, d) + dXs
+        return acq, dX[:, :q_new].contiguous()
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        """X (b x d, or b x q x d raw inputs) -> acq (b)."""
+        return self._run(X, False, None)[0]
+
+    def forward_backward(self, X: torch.Tensor, gout: Optional[torch.Tensor] = None):
+        """-> (acq (b), d sum_c gout_c acq_c / dX shaped like X); the pending points' rows are
+        dropped."""
+        if gout is not None:
+            gout = gout.to(device=self.dev, dtype=torch.float64).contiguous()
+        acq, dX = self._run(X, True, gout)
+        return acq, (dX[:, 0] if X.dim() == 2 else dX)

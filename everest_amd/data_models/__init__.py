@@ -2,8 +2,8 @@ from .domain import (BaseModel, CategoricalInput, CloseToTargetObjective, Constr
                      ContinuousInput, ContinuousOutput, Domain, Inputs, LinearEqualityConstraint,
                      LinearInequalityConstraint, MaximizeObjective, MaximizeSigmoidObjective, MinimizeObjective,
                      MinimizeSigmoidObjective, MovingMaximizeSigmoidObjective, Outputs, TargetObjective)
-from .models import (AdditiveSoboStrategy, AnyStrategy, BotorchSurrogates, CategoricalEncodingEnum, CategoricalMethodEnum,
+from .models import (ActiveLearningStrategy, AdditiveSoboStrategy, AnyActiveLearningAcquisitionFunction, AnyStrategy, BotorchSurrogates, CategoricalEncodingEnum, CategoricalMethodEnum,
                      DimensionalityScaledLogNormalPrior, GammaPrior, LogNormalPrior, MaternKernel, NormalPrior,
                      QehviStrategy, QnehviStrategy, QparegoStrategy, RandomStrategy, RBFKernel, ScalerEnum, SingleTaskGPSurrogate,
                      SoboStrategy, MoboStrategy, qEHVI, qEI, qLogEHVI, qLogEI, qLogNEHVI, qLogNEI, qNEHVI,
-                     qNEI)
+                     qNegIntPosVar, qNEI)

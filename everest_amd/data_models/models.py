@@ -14,7 +14,7 @@ import math
 from enum import Enum
 from typing import Annotated, Dict, List, Literal, Optional, Union
 
-from pydantic import Field, PositiveInt, field_validator, model_validator
+from pydantic import Field, PositiveFloat, PositiveInt, field_validator, model_validator
 
 from .domain import (BaseModel, CategoricalInput, CloseToTargetObjective, ConstrainedObjective, ContinuousOutput,
                      Domain, Inputs, MaximizeObjective, MinimizeObjective, Objective, Outputs)
@@ -240,6 +240,18 @@ AnyMultiObjectiveAcquisitionFunction = Annotated[Union[qEHVI, qLogEHVI, qNEHVI, 
 AnySingleObjectiveAcquisitionFunction = Annotated[Union[qEI, qLogEI, qNEI, qLogNEI], Field(discriminator="type")]
 
 
+class qNegIntPosVar(_AcqfMC):
+    """bofire/data_models/acquisition_functions/acquisition_function.py:86-89: n_mc_samples is the
+    number of integration points; weights (by output key, not normalised) scalarise several
+    outputs."""
+    type: Literal["qNegIntPosVar"] = "qNegIntPosVar"
+    n_mc_samples: IntPowerOfTwo = 512
+    weights: Optional[Dict[str, PositiveFloat]] = None
+
+
+AnyActiveLearningAcquisitionFunction = qNegIntPosVar
+
+
 # ---------------------------------------------------------------------------------------
 # strategies
 # ---------------------------------------------------------------------------------------
@@ -435,6 +447,22 @@ class AdditiveSoboStrategy(BotorchStrategy):
         return v
 
 
+class ActiveLearningStrategy(BotorchStrategy):
+    """bofire/data_models/strategies/predictives/active_learning.py:14-62: pure exploration, the
+    candidates that most reduce the integrated posterior variance.  Every objective type is
+    allowed."""
+    type: Literal["ActiveLearningStrategy"] = "ActiveLearningStrategy"
+    acquisition_function: AnyActiveLearningAcquisitionFunction = Field(default_factory=qNegIntPosVar)
+
+    @model_validator(mode="after")
+    def validate_acquisition_function(self):
+        w = self.acquisition_function.weights
+        if w is not None and sorted(w.keys()) != sorted(self.domain.outputs.get_keys()):
+            raise ValueError("The keys provided for the weights do not match the required keys of the output "
+                             "features.")
+        return self
+
+
 AnyStrategy = Annotated[Union[QnehviStrategy, QehviStrategy, MoboStrategy, QparegoStrategy, SoboStrategy,
-                              AdditiveSoboStrategy, RandomStrategy],
+                              AdditiveSoboStrategy, ActiveLearningStrategy, RandomStrategy],
                         Field(discriminator="type")]

@@ -952,6 +952,47 @@ def qei(R: torch.Tensor, c: float, ym: float, ys: float, kxx: float, z: torch.Te
     return acq, gR, flags
 
 
+def nipv_reduce(C: torch.Tensor, Vx: torch.Tensor, X: torch.Tensor, lo, inv_range, lengthscales, kind: int, noise,
+                coef, v0, n: Optional[int] = None, backward: bool = False, gout: Optional[torch.Tensor] = None):
+    """Per-candidate step of the negative integrated posterior variance (evr_nipv_reduce,
+    nipv.hip): C B x N x (b*q) posterior cross-covariances to the N integration points, Vx
+    B x ldv x (b*q) of which rows 0..n-1 per output are used (``n`` defaults to ldv; rows 0..n-1 of
+    R = M K_x pass with n = ldv - 1), X b x q x d raw candidates (point i of candidate c at column
+    c*q + i) -> (acq (b), flags (b, int32), dC like C | None, dVx B x n x (b*q) | None,
+    dXself b x q x d | None).  flags != 0: a pivot of a q x q Cholesky was <= 0."""
+    C, Vx, X = _dev(C, "C"), _dev(Vx, "Vx"), _dev(X, "X")
+    ls = _dev(lengthscales, "lengthscales")
+    if X.dim() != 3 or C.dim() != 3 or Vx.dim() != 3 or ls.dim() != 2:
+        raise ValueError("nipv_reduce: C, Vx and X are 3-D, lengthscales 2-D")
+    b, q, d = X.shape
+    B, N, bq = C.shape
+    ldv = Vx.shape[1]
+    n = ldv if n is None else int(n)
+    if bq != b * q or Vx.shape[0] != B or Vx.shape[2] != bq or tuple(ls.shape) != (B, d) or not 1 <= n <= ldv:
+        raise ValueError(f"nipv_reduce: shapes C {tuple(C.shape)} Vx {tuple(Vx.shape)} X {tuple(X.shape)} "
+                         f"ls {tuple(ls.shape)} n {n}")
+    lo, inv_range = _dev(lo, "lo"), _dev(inv_range, "inv_range")
+    noise, coef, v0 = _dev(noise, "noise"), _dev(coef, "coef"), _dev(v0, "v0")
+    if lo.numel() != d or inv_range.numel() != d or noise.numel() != B or coef.numel() != B or v0.numel() != B:
+        raise ValueError("nipv_reduce: lo / inv_range need d values, noise / coef / v0 one per output")
+    if gout is not None:
+        if not backward:
+            raise ValueError("nipv_reduce: gout weights the backward only")
+        gout = _dev(gout, "gout")
+        if gout.numel() != b:
+            raise ValueError("nipv_reduce: gout needs one value per candidate")
+    dev = C.device
+    acq = torch.empty(b, dtype=torch.float64, device=dev)
+    flags = torch.empty(b, dtype=torch.int32, device=dev)
+    dC = torch.empty_like(C) if backward else None
+    dVx = torch.empty(B, n, bq, dtype=torch.float64, device=dev) if backward else None
+    dXs = torch.empty_like(X) if backward else None
+    call("evr_nipv_reduce", _stream(), int(q), B, n, N, b, d, int(kind), C.data_ptr(), Vx.data_ptr(), ldv,
+         X.data_ptr(), lo.data_ptr(), inv_range.data_ptr(), ls.data_ptr(), noise.data_ptr(), coef.data_ptr(),
+         v0.data_ptr(), _p(gout), acq.data_ptr(), flags.data_ptr(), _p(dC), _p(dVx), _p(dXs))
+    return acq, flags, dC, dVx, dXs
+
+
 def scale_batched(X: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
     """In place X[b] *= alpha[b]."""
     if not X.is_contiguous():

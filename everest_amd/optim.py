@@ -366,6 +366,7 @@ class _FixedFeatures:
     def __init__(self, acqf, d: int, fixed: dict):
         self.acqf, self.d, self.dev = acqf, d, acqf.dev
         self.log_acqf = getattr(acqf, "log_acqf", False)
+        self.nonnegative = getattr(acqf, "nonnegative", True)
         self.fixed_idx = np.array(sorted(fixed), dtype=int)
         self.fixed_val = np.array([fixed[j] for j in sorted(fixed)], dtype=np.float64)
         self.free = [j for j in range(d) if j not in fixed]
@@ -470,7 +471,10 @@ def optimize_acqf(acqf, bounds: np.ndarray, num_restarts: int, raw_samples: int,
     stats.t_raw += time.perf_counter() - t0
 
     # 3. Boltzmann initial conditions
-    init = initialize_q_batch if getattr(acqf, "log_acqf", False) else initialize_q_batch_nonneg
+    # [upstream] optimize_acqf: initialize_q_batch_nonneg only where is_nonnegative(acq_function);
+    # the log acquisitions and those that declare ``nonnegative = False`` take the z-score form
+    signed = getattr(acqf, "log_acqf", False) or not getattr(acqf, "nonnegative", True)
+    init = initialize_q_batch if signed else initialize_q_batch_nonneg
     X0, _ = init(X_raw, Y_raw, num_restarts, gen)
     stats.init_X = X0
     if on_init is not None:

@@ -20,7 +20,7 @@ import torch
 
 from . import data_models as dm
 from . import ops
-from .acquisition import (QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI, QParegoLogEI,
+from .acquisition import (QNegIntPosVar, QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI, QParegoLogEI,
                           QParegoLogNEI, QParegoNEI, QSoboLogEI, QSoboLogNEI, QSoboNEI, prefetch_scramble)
 from .data_models.domain import CloseToTargetObjective, MaximizeObjective, MinimizeObjective
 from .optim import (OptimizeStats, hit_and_run, host_values, optimize_acqf, optimize_acqf_mixed,
@@ -1065,6 +1065,71 @@ class QparegoStrategy(BotorchStrategy):
         return self._postprocess_candidates(np.stack(chosen))
 
 
+class ActiveLearningStrategy(BotorchStrategy):
+    """bofire/strategies/predictives/active_learning.py:16-66 — pure exploration: the joint batch
+    that most reduces the GP's posterior variance integrated over the domain (QNegIntPosVar,
+    nipv.hip; [upstream] qNegIntegratedPosteriorVariance, restated from memory of BoTorch and
+    parity-unpinned).  One output: no transform (w = 1); several: w_j = 1 / ny, or the data
+    model's ``weights`` by output key, not normalised ([upstream] ScalarizedPosteriorTransform).
+    The strategy's pending candidates are appended to every candidate's q points ([upstream]
+    concatenate_pending_points).  ask, calc_acquisition, add_pending, fixed features, categorical
+    combinations and linear constraints are the base class's.
+
+    Deviations from the reference:
+    1. Integration points: the reference draws them from an unseeded RandomStrategy(domain) on
+       every _get_acqfs; here the RandomStrategy's seed is drawn from the strategy's generator —
+       the first draw of an ask — so an ask is reproducible.  Linear constraints are respected
+       (hit-and-run), as RandomStrategy does.
+    2. The reference passes the raw frame's values to the acquisition, which only works for
+       all-continuous domains; here the points go through the strategy's input transform, like
+       the candidates.
+    3. ``map(data_model, mc_points=ndarray)`` fixes the (transformed) integration points — a test
+       hook, as ``weights=`` is for qParEGO; the seed is still drawn.
+    4. A joint batch of new and pending points above MAX_JOINT_Q (12) raises ValueError, as
+       qParEGO does."""
+
+    def __init__(self, data_model, dist=None, mc_points=None, **kwargs):
+        super().__init__(data_model, dist=dist)
+        self.acquisition_function = data_model.acquisition_function
+        self.mc_points = None if mc_points is None else np.asarray(mc_points, dtype=np.float64)
+        self.last_acqf = None
+
+    def _draw_seed(self) -> int:
+        # 1..1000000: a RandomStrategy seed of 0 would count as no seed
+        return int(torch.randint(1, 1000001, (1,), generator=self.gen).item())
+
+    def _integration_points(self, seed: int) -> np.ndarray:
+        if self.mc_points is not None:
+            return self.mc_points
+        sampler = RandomStrategy(dm.RandomStrategy(domain=self.domain, seed=seed))
+        return self._transform(sampler.ask(int(self.acquisition_function.n_mc_samples)))
+
+    def _output_weights(self) -> Optional[np.ndarray]:
+        """active_learning.py:40-57, mapped to the model's output order."""
+        keys = list(self.model.output_keys)
+        w = self.acquisition_function.weights
+        if len(keys) == 1:
+            return None
+        if w is None:
+            return np.full(len(keys), 1.0 / len(keys))
+        return np.array([float(w[k]) for k in keys])
+
+    def _get_acqfs(self, n):
+        af = self.acquisition_function
+        if not isinstance(af, dm.qNegIntPosVar):
+            raise NotImplementedError(f"{type(af).__name__} is out of scope; use qNegIntPosVar()")
+        seed = self._draw_seed()                       # the first draw of the ask
+        _, X_pending = self.get_acqf_input_tensors()
+        npend = 0 if X_pending is None else len(X_pending)
+        if int(n) + npend > MAX_JOINT_Q:
+            raise ValueError(f"ActiveLearningStrategy: {n} candidates with {npend} pending points need a joint batch "
+                             f"above the device kernel's limit of {MAX_JOINT_Q} (EVR_QNG_MAX_Q)")
+        acqf = QNegIntPosVar(self.model, self._integration_points(seed), weights=self._output_weights(),
+                             X_pending_raw=X_pending)
+        self.last_acqf = acqf
+        return [acqf]
+
+
 STRATEGY_MAP = {
     dm.QnehviStrategy: QnehviStrategy,
     dm.QehviStrategy: QehviStrategy,
@@ -1072,6 +1137,7 @@ STRATEGY_MAP = {
     dm.QparegoStrategy: QparegoStrategy,
     dm.SoboStrategy: SoboStrategy,
     dm.AdditiveSoboStrategy: AdditiveSoboStrategy,
+    dm.ActiveLearningStrategy: ActiveLearningStrategy,
     dm.RandomStrategy: RandomStrategy,
 }
 

@@ -568,6 +568,24 @@ int evr_qparego_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_gen
                      const evr_parego* pg, int b, const double* X, const double* gout, double* work, double* acq,
                      double* dX);
 
+/* ---- negative integrated posterior variance (ActiveLearningStrategy) --------------------
+ * The per-candidate step of [upstream] qNegIntegratedPosteriorVariance as built by
+ * bofire/strategies/predictives/active_learning.py:16-66 (restated from memory, parity-unpinned).
+ * Per output j < B and candidate c < b of q joint points (point i at column c*q + i):
+ *   G = C^T C,  A = k_j(X_c, X_c) - Vx^T Vx + noise_j I,
+ *   acq[c] = - sum_j coef_j (v0_j - tr(A^-1 G) / N).
+ * C: B x N x (b*q) posterior cross-covariances to the N integration points; Vx: B x ldv x (b*q),
+ * rows 0..n-1 of each output used (ldv >= n: rows 0..n-1 of R = M K_x pass with ldv = n + 1);
+ * X: b x q x d raw candidates with lo / inv_range (d), ls (B x d) and the kind code for the self
+ * block; noise, coef, v0: B.  flags[c] != 0: a pivot of some output's q x q Cholesky was <= 0.
+ * Backward (dC, dVx, dXself all non-NULL, or all NULL): dC like C, dVx B x n x (b*q), dXself
+ * b x q x d (the slope through k_j(X_c, X_c), outputs summed in order), each weighted by gout
+ * (nullable, b).  No atomics; b = 0 returns 0 without a launch. */
+int evr_nipv_reduce(void* stream, int q, int B, int n, int N, int b, int d, int kind, const double* C,
+                    const double* Vx, int ldv, const double* X, const double* lo, const double* inv_range,
+                    const double* ls, const double* noise, const double* coef, const double* v0,
+                    const double* gout, double* acq, int* flags, double* dC, double* dVx, double* dXself);
+
 /* The PyTorch-ROCm operators torch.ops.everest_amd.qnehvi_*(everest_amd/csrc/torch_ops.cpp)
  * take a torch.classes.everest_amd.QnehviAcq: it copies the evr_qnehvi_state /
  * evr_qnehvi_model / evr_qn_general structs, holds references to the device tensors they
