@@ -251,8 +251,10 @@ __global__ __launch_bounds__(256) void trsm_kernel(int n, int nrhs, const double
 // gave 40, each walking its blocks alone: 0.47 ms at n = 280).  Wave w solves columns
 // 4w .. 4w + 3; within a wave, 16 lanes share a column, lane rg owning rows rg + 16a of the
 // current 64-row block.  Solved rows stay in LDS for the later blocks' updates.  Per row the
-// subtractions run in trsm_kernel's order (earlier blocks' q ascending, then the diagonal
-// block's q ascending) with the same contractions, and the division last: bitwise its result.
+// subtractions run over the earlier blocks' q ascending, then the diagonal block's q ascending,
+// and the division by L_rr comes last, so Higham's Thm 8.5 applies as it does to trsm_kernel:
+// |L X - B| <= gamma(n) |L||X| per element, which tests/test_gpu_linalg_reference.py holds both
+// kernels to (no test compares the two kernels' results with each other).
 constexpr int TS_C = 16, TS_MAXN = 512;
 __global__ __launch_bounds__(256) void trsm16_kernel(int n, int nrhs, const double* __restrict__ Lm, long long sL,
                                                      int ldl, double* __restrict__ Bm, long long sB, int ldb) {
@@ -499,7 +501,10 @@ __device__ __forceinline__ int panel_factor16(double (*A)[BNB + 1], double (*X)[
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int c = q + 4 * k;
-    A[c0 + r][c0 + c] = (c <= r) ? a[k] / sqrt(piv[c]) : 0.0;
+    // the diagonal holds its own pivot (a[k] == piv[r] there): sqrt(p), one rounding, where
+    // p / sqrt(p) makes two and left a 1 x 1 factor 1.1 gamma(2) off (tests/test_gpu_linalg_reference.py)
+    const double sp = sqrt(piv[c]);
+    A[c0 + r][c0 + c] = (c < r) ? a[k] / sp : (c == r ? sp : 0.0);
     X[c0 + r][c0 + c] = (c <= r) ? e[k] / sqrt(piv[r]) : 0.0;
   }
   return -1;
@@ -601,7 +606,10 @@ __device__ __forceinline__ int factor_diag64(double (*A)[BNB + 1], double (*X)[B
 }
 
 // store a factored diagonal block: L_kk (rows/cols < nb, lower) and inv(L_kk) (identity
-// padding beyond nb, ld BNB)
+// padding beyond nb, ld BNB).  The callers load the block with zeros above the diagonal and
+// neither panel_factor16 nor the panel / trailing steps write there, so the (c <= i) selects
+// below repeat what A and X already hold: they state the layout, they are not what makes L's
+// upper triangle zero
 __device__ __forceinline__ void store_diag64(const double (*A)[BNB + 1], const double (*X)[BNB + 1], int nb, double* L, int ldl,
                              int k0, double* Di) {
   for (int e = threadIdx.x; e < BNB * BNB; e += 256) {

@@ -122,8 +122,14 @@ int evr_gemm_f64(void* stream, int transA, int transB, int M, int N, int K, doub
                  long long strideB, double beta, double* C, int ldc, long long strideC, int batch);
 
 /* Batched Cholesky with [upstream] linear_operator psd_safe_cholesky semantics: plain
- * attempt, then total diagonal jitter jitter0*10^(t-1) for t = 1..max_tries; info[b] = 0
- * on success, 1 if still not p.d. (NotPSDError).  A and L must not alias.
+ * attempt, then total diagonal jitter jitter0*10^(t-1) for t = 1..max_tries.  info[b] = 0
+ * on success; otherwise member b is still not p.d. after the last attempt (NotPSDError) and
+ * info[b] = k + 1, k the first pivot of that attempt that is not positive (NaN included):
+ * LAPACK potrf's index.  L of a failed member is unspecified.  A and L must not alias.
+ * Only the lower triangle of A (j <= i) is read: the strict upper triangle may hold anything,
+ * NaN included.  L's strict upper triangle is written as zeros.  lda / ldl >= n; the
+ * elements of each row from column n to ld - 1 and the gaps between batch members
+ * (stride >= n * ld) are neither read nor written.
  * Replaces the Cholesky behind GPyTorch exact inference (K + sigma^2 I), the qNEHVI
  * baseline root (bofire/strategies/predictives/qnehvi.py:46, cache_root=True) and the
  * prune-sampling root (qnehvi.py:44, prune_baseline=True). */
@@ -132,7 +138,9 @@ int evr_cholesky(void* stream, int batch, int n, const double* A, int lda, long 
                  double* jitter_used, int* info);
 
 /* evr_cholesky plus L^-1 (Linv) from the same blocked pass (diagonal-block inverses are
- * by-products of the factorisation).  A, L and Linv must not alias. */
+ * by-products of the factorisation).  A, L and Linv must not alias.  Linv is lower
+ * triangular with an exactly zero strict upper triangle; info and the operand layout as for
+ * evr_cholesky (Linv of a failed member is unspecified). */
 int evr_cholesky_inverse(void* stream, int batch, int n, const double* A, int lda, long long strideA,
                          double* L, int ldl, long long strideL, double* Linv, int ldi,
                          long long strideI, double jitter0, int max_tries, double* jitter_used,
