@@ -82,6 +82,17 @@ class EvrParego(ctypes.Structure):
     ]
 
 
+class EvrReward(ctypes.Structure):
+    _fields_ = [
+        ("mode", c_int), ("ucb_scale", c_double), ("tau", c_double), ("best", c_void_p),
+        ("infeasible_cost", c_double), ("n_term", c_int),
+        ("term_out", c_void_p), ("term_kind", c_void_p), ("term_w", c_void_p), ("term_p0", c_void_p),
+        ("term_p1", c_void_p), ("term_p2", c_void_p),
+        ("n_con", c_int),
+        ("con_out", c_void_p), ("con_sign", c_void_p), ("con_thr", c_void_p), ("con_eta", c_void_p),
+    ]
+
+
 _SIGS = {
     "evr_version": ([], c_int),
     "evr_last_error": ([], c_char_p),
@@ -203,6 +214,11 @@ _SIGS = {
                                        c_int, c_int], c_longlong),
     "evr_qparego_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
                           POINTER(EvrParego), c_int] + [c_void_p] * 5, c_int),
+    "evr_reward_scan": ([c_void_p, c_int, c_int, c_int, c_int, POINTER(EvrReward)] + [c_void_p] * 5, c_int),
+    "evr_qreward_workspace_doubles": ([POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
+                                       c_int, c_int], c_longlong),
+    "evr_qreward_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
+                          POINTER(EvrReward), c_int] + [c_void_p] * 5, c_int),
     "evr_nipv_reduce": ([c_void_p] + [c_int] * 7 + [c_void_p] * 2 + [c_int] + [c_void_p] * 13, c_int),
     "evr_objective_general": ([c_void_p, c_int, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 4, c_int),
     "evr_objective_weights": ([c_void_p, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 3, c_int),

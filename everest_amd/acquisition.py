@@ -1476,6 +1476,139 @@ class QSoboLogEI(_SoboAcqf):
         return ops.sobol_normal(self.S, q * self.m, self.sampler_seed, self.dev)
 
 
+def get_infeasible_cost(spec: "ops.SoboSpec", mean: torch.Tensor, var: torch.Tensor) -> float:
+    """[upstream] get_infeasible_cost: M = -min(0, min_x u(mu(x) - 6 sigma(x))) from the noise-free
+    posterior moments (m x n, original units) at the points x.  Restated from memory of BoTorch,
+    parity-unpinned."""
+    return float((-_lower_bound(spec, mean, var)).clamp_min(0.0).item())
+
+
+class _RewardAcqf(_SoboAcqf):
+    """Evaluation side of QSoboSR / QSoboUCB / QSoboPI: QSoboLogEI's construction (plain joint
+    samples per output, M = [L^-1; alpha^T], no baseline draw, the S x (q + n_pending) x m
+    Sobol-normal draw of the sampler seed) with the reward scans of reward_scan.hip
+    (evr_qreward_eval).  m = 1 with one affine term goes through the same chain.  No graph-captured
+    plan: the optimiser drives these through eval_host.
+
+    The reward r = (u + M) W - M ([upstream] ConstrainedMCObjective / apply_constraints), the
+    infeasible cost M ([upstream] get_infeasible_cost) and the three reductions are restated from
+    memory of BoTorch (not importable offline) and are parity-unpinned."""
+
+    _MODE = ops.REWARD_SR
+
+    def _init_reward(self, gp: GPBatch, X_train_raw, spec: "ops.SoboSpec", S: int, seed: int, X_pending_raw,
+                     beta: float = 0.2, tau: float = 1e-3, infeasible_cost: float = 0.0):
+        name = type(self).__name__
+        if not isinstance(spec, ops.SoboSpec):
+            raise TypeError(f"{name} needs an ops.SoboSpec, got {type(spec).__name__}")
+        self._check_model(gp, spec, name)
+        self.gp, self.dev, self.S, self.nb, self.spec = gp, gp.device, int(S), 0, spec
+        self.sampler_seed = int(seed)
+        self.beta, self.tau, self.infeasible_cost = float(beta), float(tau), float(infeasible_cost)
+        if self._MODE == ops.REWARD_PI:
+            Xt = torch.as_tensor(np.asarray(X_train_raw, dtype=np.float64), device=self.dev)
+            mean, var = gp.posterior(Xt)                                    # m x n each
+            self.best = _best_feasible(spec.utility(mean.T), spec.feasible(mean.T),
+                                       lambda: _lower_bound(spec, mean, var)).reshape(1)
+        else:
+            self.best = torch.zeros(1, dtype=torch.float64, device=self.dev)    # not read
+        self.M = gp.M
+        self._finish_sobo(True, False, TAU_RELU, TAU_MAX_SO, X_pending_raw)
+        self.best_f = float(self.best.item()) if self._MODE == ops.REWARD_PI else None
+        self.rw = ops.reward_struct(spec, self._MODE, self.beta, self.tau, self.best, self.infeasible_cost)
+
+    def z_base_host(self) -> None:
+        """No baseline draw (plain joint sampling)."""
+        return None
+
+    def _draw_zq(self, q: int) -> torch.Tensor:
+        return ops.sobol_normal(self.S, q * self.m, self.sampler_seed, self.dev)
+
+    def _general(self, X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
+        """X: b x q x d -> (acq (b), dX b x q x d | None) through evr_qreward_eval."""
+        b, q, d = X.shape
+        X = self._joint(X)
+        qq = X.shape[1]
+        g = _native.EvrQnGeneral()
+        g.q, g.zq = int(qq), self._zq(qq).data_ptr()
+        acq, dX = ops.qreward_eval(self.state, g, self.model, self.rw, X.reshape(b * qq, d).contiguous(), backward,
+                                   gout)
+        if dX is not None:
+            dX = dX.view(b, qq, d)[:, :q].contiguous()
+        return acq, dX
+
+    def _torch_acq(self, q: int, fast: bool = False):
+        """The torch.classes.everest_amd.QrewardAcq behind torch.ops.everest_amd.qreward_*."""
+        from . import torch_ops
+
+        torch_ops.load()
+        acq = self.__dict__.get("_torch_reward")
+        if acq is None:
+            def raw(st):
+                return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8)
+            terms = torch.tensor(self.spec.terms, dtype=torch.float64).reshape(-1, 6)
+            cons = torch.tensor(self.spec.constraints, dtype=torch.float64).reshape(-1, 4)
+            acq = torch.classes.everest_amd.QrewardAcq(raw(self.state), raw(self.model), int(self._MODE),
+                                                       float(self.rw.ucb_scale), self.tau, self.infeasible_cost,
+                                                       self.best, terms, cons, self._device_tensors())
+            self._torch_reward = acq
+        done = self.__dict__.setdefault("_torch_reward_q", set())
+        if q not in done:
+            acq.set_samples(int(q), self._zq(q))
+            done.add(q)
+        return acq
+
+    def __call__(self, X: torch.Tensor) -> torch.Tensor:
+        """X (b x q x d, or b x d for q = 1) -> acq (b), differentiable through the device
+        backward (torch.ops.everest_amd.qreward_forward / qreward_forward_backward)."""
+        from .torch_ops import QrewardFunction
+
+        X3 = self._joint(self._split(X)[0]).contiguous()
+        return QrewardFunction.apply(X3, self._torch_acq(X3.shape[1]))
+
+
+class QSoboSR(_RewardAcqf):
+    """Device qSR — [upstream] qSimpleRegret over m model outputs with the utility of ``spec``
+    (ops.SoboSpec): acq = mean_s max_i r_si, r = (u + M) W - M when the spec carries output
+    constraints (absorbed into the objective with the infeasible cost M, as
+    bofire/strategies/predictives/sobo.py:130-145 does), r = u otherwise.  Values are signed
+    (``nonnegative = False``: optimize_acqf takes initialize_q_batch).  Parity-unpinned
+    (_RewardAcqf)."""
+
+    _MODE = ops.REWARD_SR
+    nonnegative = False
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, spec: "ops.SoboSpec", S: int = 512, seed: int = 0,
+                 X_pending_raw: Optional[np.ndarray] = None, infeasible_cost: float = 0.0):
+        self._init_reward(gp, X_train_raw, spec, S, seed, X_pending_raw, infeasible_cost=infeasible_cost)
+
+
+class QSoboUCB(_RewardAcqf):
+    """Device qUCB — [upstream] qUpperConfidenceBound over the reward of QSoboSR:
+    acq = mean_s max_i ( rbar_i + sqrt(beta pi / 2) |r_si - rbar_i| ), rbar_i the sample mean of
+    point i's reward (pending points included).  Values are signed (``nonnegative = False``).
+    Parity-unpinned (_RewardAcqf)."""
+
+    _MODE = ops.REWARD_UCB
+    nonnegative = False
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, spec: "ops.SoboSpec", beta: float = 0.2, S: int = 512,
+                 seed: int = 0, X_pending_raw: Optional[np.ndarray] = None, infeasible_cost: float = 0.0):
+        self._init_reward(gp, X_train_raw, spec, S, seed, X_pending_raw, beta=beta, infeasible_cost=infeasible_cost)
+
+
+class QSoboPI(_RewardAcqf):
+    """Device qPI — [upstream] qProbabilityOfImprovement: acq = mean_s max_i
+    [ sigmoid((u_si - best_f) / tau) W_si ], the output constraints of ``spec`` kept separate
+    ([upstream] SampleReducingMCAcquisitionFunction._apply_constraints on a non-negative
+    acquisition) and best_f the scalar incumbent of QSoboLogEI.  Parity-unpinned (_RewardAcqf)."""
+
+    _MODE = ops.REWARD_PI
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, spec: "ops.SoboSpec", tau: float = 1e-3, S: int = 512,
+                 seed: int = 0, X_pending_raw: Optional[np.ndarray] = None):
+        self._init_reward(gp, X_train_raw, spec, S, seed, X_pending_raw, tau=tau)
+
 
 def _need_parego(spec, name: str):
     if not isinstance(spec, ops.ParegoSpec):

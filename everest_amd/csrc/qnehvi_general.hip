@@ -1225,6 +1225,8 @@ int sobo_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_
                      const int* flags, const double* gout, double* acq, double* dY);
 int parego_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_parego* pg, const double* Y,
                        const int* flags, const double* gout, double* acq, double* dY);
+int reward_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_reward* rw, const double* Y,
+                       const int* flags, const double* gout, double* acq, double* dY);
 
 struct QnLayout {
   size_t Kx, R, P, Wf, Y, Lq, flags, dY, cf, dKqq, cm, gR, dKx, Wb, kg, total;
@@ -1394,6 +1396,23 @@ int evr_qparego_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_gen
   return qn_chain("evr_qparego_eval", s, stm, g, md, b, X, work, acq, dX,
                   [&](int q, int m, int S, const double* Y, const int* flags, double* dY) {
                     return parego_scan_launch(s, q, m, S, b, pg, Y, flags, gout, acq, dY);
+                  });
+}
+
+// qSobo SR / UCB / PI: the chain with the reward scans of reward_scan.hip.
+long long evr_qreward_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                        const evr_qnehvi_model* md, int b, int backward) {
+  return qn_workspace_doubles(stm, g, md, b, backward);
+}
+
+int evr_qreward_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                     const evr_reward* rw, int b, const double* X, const double* gout, double* work, double* acq,
+                     double* dX) {
+  EVR_CHECK(stm && g && md && rw, "evr_qreward_eval: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  return qn_chain("evr_qreward_eval", s, stm, g, md, b, X, work, acq, dX,
+                  [&](int q, int m, int S, const double* Y, const int* flags, double* dY) {
+                    return reward_scan_launch(s, q, m, S, b, rw, Y, flags, gout, acq, dY);
                   });
 }
 

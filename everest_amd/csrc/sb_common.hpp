@@ -41,6 +41,20 @@ __device__ __forceinline__ double sb_dterm(const SbTab& t, int k, double y) {
   return st * qg_sig(x1) * qg_sig(-x2) * (qg_sig(-x1) - qg_sig(x2));
 }
 
+// utilities u(y) = sum_t w_t g_t(y[out_t]) of the Q points of one (sample, candidate) (Ys, st as
+// in sb_feas below).  The term loop is the outer one, as in sobo_scan.hip's sb_points.
+template <int Q>
+__device__ __forceinline__ void sb_util(const SbTab& t, const double* __restrict__ Ys, size_t st, double* u) {
+#pragma unroll
+  for (int i = 0; i < Q; ++i) u[i] = 0.0;
+  for (int k = 0; k < t.o.mo; ++k) {
+    const double* Yk = Ys + (size_t)t.o.oo[k] * st;
+    const double wk = t.w[k];
+#pragma unroll
+    for (int i = 0; i < Q; ++i) u[i] += wk * sb_term(t, k, Yk[i]);
+  }
+}
+
 // summed log feasibilities of the Q points of one (sample, candidate), added to lw (log-sigmoid
 // in plain mode, log-fatmoid in log mode).  Ys: the output-0 sample of point 0, outputs `st`
 // doubles apart.  The constraint loop is the outer one: one set of scalar table reads per

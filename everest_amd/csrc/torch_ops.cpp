@@ -587,9 +587,121 @@ std::tuple<at::Tensor, at::Tensor> qparego_forward_backward(const ParegoPtr& acq
   return acq->eval(X, true);
 }
 
+// ---------------------------------------------------------------------------------------
+// The acquisition behind torch.ops.everest_amd.qreward_*: qSR / qUCB / qPI over several model
+// outputs (reward scans of reward_scan.hip) through evr_qreward_eval.  Ownership as in QsoboAcq.
+// ---------------------------------------------------------------------------------------
+struct QrewardAcq : torch::CustomClassHolder {
+  evr_qnehvi_state stm{};
+  evr_qnehvi_model md{};
+  evr_reward rw{};
+  std::vector<int> to, tk, co;
+  std::vector<double> tw, tp0, tp1, tp2, cs, ct, ce;
+  at::Tensor best;
+  std::vector<at::Tensor> keep;
+  std::map<int64_t, at::Tensor> zqs;
+  int64_t n_evals = 0;
+
+  // mode: EVR_REWARD_*; best: one double (read by qPI only); terms / cons as in QsoboAcq
+  QrewardAcq(const at::Tensor& stm_b, const at::Tensor& md_b, int64_t mode, double ucb_scale, double tau,
+             double infeasible_cost, const at::Tensor& best_, const at::Tensor& terms_, const at::Tensor& cons_,
+             std::vector<at::Tensor> keep_)
+      : keep(std::move(keep_)) {
+    stm = QnehviAcq::from_bytes<evr_qnehvi_state>(stm_b, "model-side state");
+    md = QnehviAcq::from_bytes<evr_qnehvi_model>(md_b, "model");
+    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m >= 1,
+                "QrewardAcq: inconsistent model");
+    best = dev64(best_, "best");
+    TORCH_CHECK(best.numel() == 1, "QrewardAcq: best needs one value");
+    auto T = terms_.to(at::kCPU, at::kDouble).contiguous();
+    auto C = cons_.to(at::kCPU, at::kDouble).contiguous();
+    TORCH_CHECK(T.dim() == 2 && T.size(1) == 6 && T.size(0) >= 1 && T.size(0) <= EVR_SOBO_MAX_TERMS,
+                "QrewardAcq: terms must be n_term x 6, 1..", EVR_SOBO_MAX_TERMS, " rows");
+    TORCH_CHECK(C.numel() == 0 || (C.dim() == 2 && C.size(1) == 4), "QrewardAcq: constraints must be n_con x 4");
+    const double* t = T.data_ptr<double>();
+    for (int64_t k = 0; k < T.size(0); ++k, t += 6) {
+      to.push_back((int)t[0]);
+      tk.push_back((int)t[1]);
+      tw.push_back(t[2]);
+      tp0.push_back(t[3]);
+      tp1.push_back(t[4]);
+      tp2.push_back(t[5]);
+    }
+    const int64_t nc = C.numel() / 4;
+    const double* c = nc ? C.data_ptr<double>() : nullptr;
+    for (int64_t e = 0; e < nc; ++e, c += 4) {
+      co.push_back((int)c[0]);
+      cs.push_back(c[1]);
+      ct.push_back(c[2]);
+      ce.push_back(c[3]);
+    }
+    rw.mode = (int)mode;
+    rw.ucb_scale = ucb_scale;
+    rw.tau = tau;
+    rw.best = best.data_ptr<double>();
+    rw.infeasible_cost = infeasible_cost;
+    rw.n_term = (int)to.size();
+    rw.term_out = to.data();
+    rw.term_kind = tk.data();
+    rw.term_w = tw.data();
+    rw.term_p0 = tp0.data();
+    rw.term_p1 = tp1.data();
+    rw.term_p2 = tp2.data();
+    rw.n_con = (int)nc;
+    rw.con_out = nc ? co.data() : nullptr;
+    rw.con_sign = nc ? cs.data() : nullptr;
+    rw.con_thr = nc ? ct.data() : nullptr;
+    rw.con_eta = nc ? ce.data() : nullptr;
+  }
+
+  void set_samples(int64_t q, const at::Tensor& zq) {
+    TORCH_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "QrewardAcq.set_samples: q = ", q, " outside 1..", EVR_QNG_MAX_Q);
+    auto z = dev64(zq, "zq");
+    TORCH_CHECK(z.numel() == (int64_t)stm.S * q * stm.m, "QrewardAcq.set_samples: zq must be S x q x m");
+    zqs[q] = z;
+  }
+
+  std::tuple<at::Tensor, at::Tensor> eval(const at::Tensor& X_, bool backward) {
+    auto X = dev64(X_, "X");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+    hipStream_t s = cur_stream();
+    TORCH_CHECK(X.dim() == 3 && X.size(2) == md.d, "qreward: X must be b x q x d");
+    const int64_t b = X.size(0), q = X.size(1);
+    auto it = zqs.find(q);
+    TORCH_CHECK(it != zqs.end(), "qreward: no base samples set for q = ", q);
+    evr_qn_general g{};
+    g.q = (int)q;
+    g.zq = it->second.data_ptr<double>();
+    auto acq = at::empty({b}, X.options());
+    at::Tensor dX = backward ? at::empty_like(X) : at::Tensor();
+    if (b == 0) return {acq, dX};
+    auto work = scratch(evr_qreward_workspace_doubles(&stm, &g, &md, (int)b, backward), X);
+    check(evr_qreward_eval(s, &stm, &g, &md, &rw, (int)b, X.data_ptr<double>(), nullptr, work.data_ptr<double>(),
+                           acq.data_ptr<double>(), backward ? dX.data_ptr<double>() : nullptr),
+          "qreward_eval");
+    ++n_evals;
+    return {acq, dX};
+  }
+
+  int64_t evals() const { return n_evals; }
+};
+
+using RewardPtr = c10::intrusive_ptr<QrewardAcq>;
+
+at::Tensor qreward_forward(const RewardPtr& acq, const at::Tensor& X) { return std::get<0>(acq->eval(X, false)); }
+
+std::tuple<at::Tensor, at::Tensor> qreward_forward_backward(const RewardPtr& acq, const at::Tensor& X) {
+  return acq->eval(X, true);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(everest_amd, m) {
+  m.class_<QrewardAcq>("QrewardAcq")
+      .def(torch::init<at::Tensor, at::Tensor, int64_t, double, double, double, at::Tensor, at::Tensor, at::Tensor,
+                       std::vector<at::Tensor>>())
+      .def("set_samples", &QrewardAcq::set_samples)
+      .def("evals", &QrewardAcq::evals);
   m.class_<QparegoAcq>("QparegoAcq")
       .def(torch::init<at::Tensor, at::Tensor, bool, double, double, at::Tensor, double, at::Tensor, at::Tensor,
                        std::vector<at::Tensor>>())
@@ -625,6 +737,8 @@ TORCH_LIBRARY(everest_amd, m) {
   m.def("qsobo_forward_backward(__torch__.torch.classes.everest_amd.QsoboAcq acq, Tensor X) -> (Tensor, Tensor)");
   m.def("qparego_forward(__torch__.torch.classes.everest_amd.QparegoAcq acq, Tensor X) -> Tensor");
   m.def("qparego_forward_backward(__torch__.torch.classes.everest_amd.QparegoAcq acq, Tensor X) -> (Tensor, Tensor)");
+  m.def("qreward_forward(__torch__.torch.classes.everest_amd.QrewardAcq acq, Tensor X) -> Tensor");
+  m.def("qreward_forward_backward(__torch__.torch.classes.everest_amd.QrewardAcq acq, Tensor X) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(everest_amd, CUDA, m) {
@@ -642,4 +756,6 @@ TORCH_LIBRARY_IMPL(everest_amd, CUDA, m) {
   m.impl("qsobo_forward_backward", &qsobo_forward_backward);
   m.impl("qparego_forward", &qparego_forward);
   m.impl("qparego_forward_backward", &qparego_forward_backward);
+  m.impl("qreward_forward", &qreward_forward);
+  m.impl("qreward_forward_backward", &qreward_forward_backward);
 }

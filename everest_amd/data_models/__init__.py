@@ -6,4 +6,4 @@ from .models import (ActiveLearningStrategy, AdditiveSoboStrategy, AnyActiveLear
                      DimensionalityScaledLogNormalPrior, GammaPrior, LogNormalPrior, MaternKernel, NormalPrior,
                      QehviStrategy, QnehviStrategy, QparegoStrategy, RandomStrategy, RBFKernel, ScalerEnum, SingleTaskGPSurrogate,
                      SoboStrategy, MoboStrategy, qEHVI, qEI, qLogEHVI, qLogEI, qLogNEHVI, qLogNEI, qNEHVI,
-                     qNegIntPosVar, qNEI)
+                     qNegIntPosVar, qNEI, qPI, qSR, qUCB)

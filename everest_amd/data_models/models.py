@@ -209,6 +209,23 @@ class qLogNEI(_AcqfMC):
     n_mc_samples: int = 512
 
 
+class qSR(_AcqfMC):
+    type: Literal["qSR"] = "qSR"
+    n_mc_samples: int = 512
+
+
+class qUCB(_AcqfMC):
+    type: Literal["qUCB"] = "qUCB"
+    beta: Annotated[float, Field(ge=0)] = 0.2
+    n_mc_samples: int = 512
+
+
+class qPI(_AcqfMC):
+    type: Literal["qPI"] = "qPI"
+    tau: PositiveFloat = 1e-3
+    n_mc_samples: int = 512
+
+
 class qEHVI(_AcqfMC):
     type: Literal["qEHVI"] = "qEHVI"
     alpha: Annotated[float, Field(ge=0)] = 0.0
@@ -237,7 +254,8 @@ class qLogNEHVI(_AcqfMC):
 
 AnyMultiObjectiveAcquisitionFunction = Annotated[Union[qEHVI, qLogEHVI, qNEHVI, qLogNEHVI],
                                                  Field(discriminator="type")]
-AnySingleObjectiveAcquisitionFunction = Annotated[Union[qEI, qLogEI, qNEI, qLogNEI], Field(discriminator="type")]
+AnySingleObjectiveAcquisitionFunction = Annotated[Union[qEI, qLogEI, qNEI, qLogNEI, qSR, qUCB, qPI],
+                                                  Field(discriminator="type")]
 
 
 class qNegIntPosVar(_AcqfMC):

@@ -9,6 +9,7 @@ custom operators (``torch.ops.everest_amd.*``, everest_amd/csrc/torch_ops.cpp, e
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import warnings
 from typing import Optional, Tuple
@@ -787,6 +788,80 @@ def qparego_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehvi
     """qParEGO's qNEI, qLogNEI, qLogEI, qEI over m model outputs (evr_qparego_eval):
     X (b*q) x d raw candidates -> acq (b) [, dX (b*q) x d]."""
     return _utility_eval("evr_qparego", stm, g, model, pg, X, backward, gout)
+
+
+REWARD_SR, REWARD_UCB, REWARD_PI = 0, 1, 2
+
+
+def ucb_scale(beta: float) -> float:
+    """[upstream] qUpperConfidenceBound: k = sqrt(beta pi / 2)."""
+    beta = float(beta)
+    if not (beta >= 0.0 and math.isfinite(beta)):
+        raise ValueError(f"qUCB: beta = {beta} must be non-negative and finite")
+    return math.sqrt(beta * math.pi / 2.0)
+
+
+def reward_struct(spec: SoboSpec, mode: int, beta: float = 0.2, tau: float = 1e-3,
+                  best: Optional[torch.Tensor] = None, infeasible_cost: float = 0.0) -> "_native.EvrReward":
+    """evr_reward over the tables of ``spec``: mode REWARD_SR / REWARD_UCB (beta) / REWARD_PI (tau
+    and ``best``, one device double).  infeasible_cost: M >= 0 of the constrained reward (SR /
+    UCB).  The struct points into the spec's host arrays and into ``best``: keep both alive."""
+    if mode not in (REWARD_SR, REWARD_UCB, REWARD_PI):
+        raise ValueError(f"reward scan: mode {mode}")
+    if not isinstance(spec, SoboSpec):
+        raise TypeError(f"reward scan needs an ops.SoboSpec, got {type(spec).__name__}")
+    rw = _native.EvrReward()
+    rw.mode = int(mode)
+    rw.ucb_scale = ucb_scale(beta) if mode == REWARD_UCB else 0.0
+    rw.tau = float(tau)
+    if mode == REWARD_PI:
+        if best is None or best.numel() != 1:
+            raise ValueError("qPI needs the incumbent: one device double")
+        if not float(tau) > 0.0:
+            raise ValueError(f"qPI: tau = {tau} must be positive")
+        rw.best = _dev(best, "best").data_ptr()
+    else:
+        if not float(infeasible_cost) >= 0.0:
+            raise ValueError(f"reward scan: infeasible cost {infeasible_cost} must be non-negative")
+    rw.infeasible_cost = float(infeasible_cost)
+    rw.n_term, rw.n_con = len(spec.terms), len(spec.constraints)
+    (rw.term_out, rw.term_kind, rw.term_w, rw.term_p0, rw.term_p1,
+     rw.term_p2) = (a.ctypes.data for a in spec._tarrs)
+    rw.con_out, rw.con_sign, rw.con_thr, rw.con_eta = (a.ctypes.data for a in spec._carrs)
+    return rw
+
+
+def reward_scan(Y: torch.Tensor, q: int, spec: SoboSpec, mode: int, beta: float = 0.2, tau: float = 1e-3,
+                best: Optional[torch.Tensor] = None, infeasible_cost: float = 0.0,
+                flags: Optional[torch.Tensor] = None, gout: Optional[torch.Tensor] = None, backward: bool = False):
+    """qSR / qUCB / qPI scan alone (evr_reward_scan): Y S x m_model x (b*q) joint samples (point i
+    of candidate c at column c*q + i) -> (acq (b), dY like Y | None).  flags: m_model x b."""
+    Y = _dev(Y, "Y")
+    S, m, bq = Y.shape
+    q = int(q)
+    if m != spec.m_model:
+        raise ValueError(f"Y has {m} outputs, the spec {spec.m_model}")
+    if q < 1 or bq % q:
+        raise ValueError(f"{bq} columns are not a multiple of q = {q}")
+    b = bq // q
+    best = None if best is None else _dev(best, "best")
+    flags = None if flags is None else _dev(flags, "flags", torch.int32)
+    gout = None if gout is None else _dev(gout, "gout")
+    if (flags is not None and flags.numel() != m * b) or (gout is not None and gout.numel() != b):
+        raise ValueError("flags need one entry per (output, candidate), gout one per candidate")
+    acq = torch.empty(b, dtype=torch.float64, device=Y.device)
+    dY = torch.empty_like(Y) if backward else None
+    rw = reward_struct(spec, mode, beta, tau, best, infeasible_cost)
+    call("evr_reward_scan", _stream(), q, m, S, b, ctypes.byref(rw), Y.data_ptr(), _p(flags), _p(gout),
+         acq.data_ptr(), _p(dY))
+    return acq, dY
+
+
+def qreward_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviModel", rw: "_native.EvrReward",
+                 X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
+    """qSR, qUCB, qPI over m model outputs (evr_qreward_eval): X (b*q) x d raw candidates -> acq (b)
+    [, dX (b*q) x d]."""
+    return _utility_eval("evr_qreward", stm, g, model, rw, X, backward, gout)
 
 
 class QnehviPlan:

@@ -21,7 +21,8 @@ import torch
 from . import data_models as dm
 from . import ops
 from .acquisition import (QNegIntPosVar, QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI, QParegoLogEI,
-                          QParegoLogNEI, QParegoNEI, QSoboLogEI, QSoboLogNEI, QSoboNEI, prefetch_scramble)
+                          QParegoLogNEI, QParegoNEI, QSoboLogEI, QSoboLogNEI, QSoboNEI, QSoboPI, QSoboSR, QSoboUCB,
+                          get_infeasible_cost, prefetch_scramble)
 from .data_models.domain import CloseToTargetObjective, MaximizeObjective, MinimizeObjective
 from .optim import (OptimizeStats, hit_and_run, host_values, optimize_acqf, optimize_acqf_mixed,
                     prefetch_raw_samples)
@@ -344,6 +345,21 @@ class BotorchStrategy(PredictiveStrategy):
         if combined:
             X = X.unsqueeze(0)
         return host_values(acqf.forward(X))
+
+    def get_infeasible_cost(self, spec: ops.SoboSpec, n_samples: int = 128) -> float:
+        """bofire/strategies/predictives/botorch.py:726-750: [upstream] get_infeasible_cost
+        M = -min(0, min_x u(mu(x) - 6 sigma(x))) of the utility of ``spec`` over X_train, the
+        pending points and ``n_samples`` points of a RandomStrategy on the domain.  The reference's
+        RandomStrategy is unseeded; here its seed is one draw from the strategy's generator, so an
+        ask is reproducible.  Restated from memory of BoTorch, parity-unpinned."""
+        seed = int(torch.randint(1, 1000001, (1,), generator=self.gen).item())   # 0 would count as no seed
+        X_train, X_pending = self.get_acqf_input_tensors()
+        sampler = RandomStrategy(dm.RandomStrategy(domain=self.domain, seed=seed))
+        parts = [X_train] + ([X_pending] if X_pending is not None else [])
+        parts.append(self._transform(sampler.ask(int(n_samples))))
+        X = torch.as_tensor(np.concatenate(parts, 0), dtype=torch.float64, device=self.model.device)
+        mean, var = self.model.posterior(X)
+        return get_infeasible_cost(spec, mean, var)
 
     def _bounds(self) -> np.ndarray:
         lo, hi = self.domain.inputs.get_bounds(specs=self.input_preprocessing_specs)
@@ -790,13 +806,31 @@ def sobo_objective_spec(outputs, output_keys: Sequence[str], experiments: Option
     return terms, constraints
 
 
+def reward_constraint_handling(af, constraints) -> str:
+    """How qSR / qUCB / qPI treat the output constraints that ``sobo_objective_spec`` yields (host
+    only): "absorbed" — qSR and qUCB fold them into the objective with the infeasible cost M
+    (ConstrainedMCObjective, bofire/strategies/predictives/sobo.py:130-145, 192-205);
+    "separate" — qPI keeps them as the acquisition's own constraints, as qEI does; "none" — no
+    constraints, the reward is the plain utility."""
+    if not isinstance(af, (dm.qSR, dm.qUCB, dm.qPI)):
+        raise TypeError(f"{type(af).__name__} is not qSR, qUCB or qPI")
+    if not constraints:
+        return "none"
+    return "separate" if isinstance(af, dm.qPI) else "absorbed"
+
+
 class SoboStrategy(BotorchStrategy):
     """bofire/strategies/predictives/sobo.py:40-152 — qLogNEI (the data model's default), qNEI,
-    qLogEI and qEI on the device.  One affine objective on a single-output model without output
+    qLogEI, qEI, qSR, qUCB and qPI on the device.  One affine objective on a single-output model without output
     constraints runs QLogNEI / QNEI / QLogEI / QEI / QEIJoint (nei_scan.hip); every other
     shape — further outputs with MaximizeSigmoid / MinimizeSigmoid / Target objectives as output
     constraints, a sigmoid / target / close-to-target objective of its own — runs QSoboLogNEI /
-    QSoboNEI / QSoboLogEI over all model outputs (sobo_scan.hip)."""
+    QSoboNEI / QSoboLogEI over all model outputs (sobo_scan.hip).  qSR, qUCB and qPI always run
+    QSoboSR / QSoboUCB / QSoboPI (reward_scan.hip), whatever the shape.
+
+    Deviation for qSR / qUCB: the reference's additive branch (sobo.py:192-205) hands ``None``
+    constraints to ConstrainedMCObjective when ``use_output_constraints`` is set but no constraint
+    exists; here the reward then is the plain utility."""
 
     _additive = False
 
@@ -817,12 +851,15 @@ class SoboStrategy(BotorchStrategy):
 
     def _get_acqfs(self, n):
         af = self.acquisition_function
-        if not isinstance(af, (dm.qEI, dm.qLogEI, dm.qNEI, dm.qLogNEI)):
-            raise NotImplementedError(f"{type(af).__name__} is out of scope; use qLogNEI(), qNEI(), qLogEI() or qEI()")
+        if not isinstance(af, (dm.qEI, dm.qLogEI, dm.qNEI, dm.qLogNEI, dm.qSR, dm.qUCB, dm.qPI)):
+            raise NotImplementedError(f"{type(af).__name__} is out of scope; use qLogNEI(), qNEI(), qLogEI(), qEI(), "
+                                      "qSR(), qUCB() or qPI()")
         terms, constraints = self._sobo_spec()
         X_train, X_pending = self.get_acqf_input_tensors()
         S = int(af.n_mc_samples)
         m = len(self.model.output_keys)
+        if isinstance(af, (dm.qSR, dm.qUCB, dm.qPI)):
+            return self._get_reward_acqfs(af, ops.SoboSpec(m, terms, constraints), X_train, X_pending, S)
         if not (m == 1 and not constraints and len(terms) == 1 and terms[0][1] == ops.OBJ_AFFINE
                 and terms[0][2] == 1.0):
             return self._get_general_acqfs(af, ops.SoboSpec(m, terms, constraints), X_train, X_pending, S)
@@ -861,6 +898,25 @@ class SoboStrategy(BotorchStrategy):
         else:
             acqf = QSoboLogEI(self.model, X_train, spec, S=S, seed=self._draw_seed(), X_pending_raw=X_pending,
                               log=isinstance(af, dm.qLogEI))
+        self.last_acqf = acqf
+        return [acqf]
+
+
+    def _get_reward_acqfs(self, af, spec: ops.SoboSpec, X_train, X_pending, S: int):
+        """qSR / qUCB / qPI (sobo.py:64-90, 130-145): the infeasible cost's RandomStrategy seed is
+        drawn before the sampler seed, the order in which the reference calls the two."""
+        kw = dict(S=S, X_pending_raw=X_pending)
+        if isinstance(af, dm.qPI):
+            acqf = QSoboPI(self.model, X_train, spec, tau=float(af.tau), seed=self._draw_seed(), **kw)
+        else:
+            M = 0.0
+            if reward_constraint_handling(af, spec.constraints) == "absorbed":
+                M = self.get_infeasible_cost(spec)
+            seed = self._draw_seed()
+            if isinstance(af, dm.qUCB):
+                acqf = QSoboUCB(self.model, X_train, spec, beta=float(af.beta), seed=seed, infeasible_cost=M, **kw)
+            else:
+                acqf = QSoboSR(self.model, X_train, spec, seed=seed, infeasible_cost=M, **kw)
         self.last_acqf = acqf
         return [acqf]
 

@@ -17,6 +17,9 @@ AcquisitionFunction.forward protocols called at bofire/strategies/predictives/bo
     torch.ops.everest_amd.qsobo_forward / qsobo_forward_backward   (scalarised / output-constrained SOBO)
     torch.classes.everest_amd.QparegoAcq(state, model, log, tau_relu, tau_max, best, alpha, terms, constraints, keep)
     torch.ops.everest_amd.qparego_forward / qparego_forward_backward   (qParEGO: augmented Chebyshev utility)
+    torch.classes.everest_amd.QrewardAcq(state, model, mode, ucb_scale, tau, infeasible_cost, best, terms,
+                                         constraints, keep)
+    torch.ops.everest_amd.qreward_forward / qreward_forward_backward   (qSR, qUCB, qPI)
 
 No fallback: a missing library raises NativeLibraryError."""
 from __future__ import annotations
@@ -124,6 +127,26 @@ class QparegoFunction(torch.autograd.Function):
             return a
         ctx.save_for_backward(None)
         return ops.qparego_forward(acq, X)
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        (dX,) = ctx.saved_tensors
+        return dX * grad_out.reshape(-1, 1, 1), None
+
+
+class QrewardFunction(torch.autograd.Function):
+    """acq = QSoboSR / QSoboUCB / QSoboPI(X), X b x q x d, through torch.ops.everest_amd.qreward_*
+    on a torch.classes.everest_amd.QrewardAcq; as QneiFunction."""
+
+    @staticmethod
+    def forward(ctx, X: torch.Tensor, acq):
+        ops = load()
+        if ctx.needs_input_grad[0]:
+            a, dX = ops.qreward_forward_backward(acq, X)
+            ctx.save_for_backward(dX)
+            return a
+        ctx.save_for_backward(None)
+        return ops.qreward_forward(acq, X)
 
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):

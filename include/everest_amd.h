@@ -576,6 +576,59 @@ int evr_qparego_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_gen
                      const evr_parego* pg, int b, const double* X, const double* gout, double* work, double* acq,
                      double* dX);
 
+/* ---- reward scans qSR / qUCB / qPI with output constraints (reward_scan.hip) ---------------
+ * The step between the joint samples Y of q-point candidates and dY for the three
+ * single-objective acquisitions that are not an improvement over a per-sample incumbent, over
+ * the utility u(y) = sum_t w_t g_t(y[out_t]) and the constraints of evr_sobo_scan (same term
+ * kinds, same tables).  W = exp(sum_c logsigmoid(-c/eta)) (plain sigmoid; 1 without constraints).
+ * Restated from memory of BoTorch (parity-unpinned):
+ *   reward ([upstream] ConstrainedMCObjective / apply_constraints, as bofire/strategies/
+ *   predictives/sobo.py:130-145, 192-205 builds it): r = (u + M) W - M with constraints, r = u
+ *   without; M = infeasible_cost >= 0.
+ *   EVR_REWARD_SR  ([upstream] qSimpleRegret):         acq_c = mean_s max_i r_sci
+ *   EVR_REWARD_UCB ([upstream] qUpperConfidenceBound): acq_c = mean_s max_i (rbar_ci + k |r_sci - rbar_ci|),
+ *                  rbar_ci = mean_s r_sci, k = ucb_scale = sqrt(beta pi / 2)
+ *   EVR_REWARD_PI  ([upstream] qProbabilityOfImprovement, constraints applied to the non-negative
+ *                  acquisition): acq_c = mean_s max_i [ sigmoid((u_sci - best[0]) / tau) W_sci ]
+ * All maxima take the first arg-max; sgn(0) = 0 in qUCB's adjoint (at S = 1 every difference is
+ * exactly zero).  Y / dY, flags, gout as in evr_sobo_scan; dY (nullable = forward only) is
+ * written in full with exact zeros for outputs nothing reads.  The term / constraint arrays are
+ * HOST arrays; best is on the device (one double, read in PI mode only).  Refused: what
+ * evr_sobo_scan refuses, an unknown mode, a negative or non-finite ucb_scale (UCB), tau <= 0
+ * (PI), infeasible_cost < 0 (SR / UCB).  Forward and backward are ONE launch each (qUCB walks Y
+ * two / three times inside it); no atomics; results are bitwise reproducible. */
+#define EVR_REWARD_SR 0
+#define EVR_REWARD_UCB 1
+#define EVR_REWARD_PI 2
+typedef struct {
+  int mode;                 /* EVR_REWARD_* */
+  double ucb_scale;         /* UCB: k = sqrt(beta pi / 2) >= 0 */
+  double tau;               /* PI: temperature > 0 */
+  const double* best;       /* device: one double, the incumbent in utility space (PI only) */
+  double infeasible_cost;   /* SR / UCB: M >= 0, read when n_con > 0 */
+  int n_term;               /* 1..EVR_SOBO_MAX_TERMS */
+  const int* term_out;
+  const int* term_kind;
+  const double* term_w;
+  const double* term_p0;
+  const double* term_p1;
+  const double* term_p2;
+  int n_con;                /* 0..16 */
+  const int* con_out;
+  const double* con_sign;
+  const double* con_thr;
+  const double* con_eta;
+} evr_reward;
+int evr_reward_scan(void* stream, int q, int m_model, int S, int b, const evr_reward* rw, const double* Y,
+                    const int* flags, const double* gout, double* acq, double* dY);
+/* Full evaluation: evr_qsobo_eval's chain (same stm / g / md / X / work / acq / dX semantics)
+ * with evr_reward_scan in place of evr_sobo_scan. */
+long long evr_qreward_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                        const evr_qnehvi_model* md, int b, int backward);
+int evr_qreward_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                     const evr_reward* rw, int b, const double* X, const double* gout, double* work, double* acq,
+                     double* dX);
+
 /* ---- negative integrated posterior variance (ActiveLearningStrategy) --------------------
  * The per-candidate step of [upstream] qNegIntegratedPosteriorVariance as built by
  * bofire/strategies/predictives/active_learning.py:16-66 (restated from memory, parity-unpinned).
