@@ -976,44 +976,113 @@ class QEIJoint(QEHVI):
 TAU_MAX_SO = 1e-2   # [upstream] botorch.acquisition.logei.TAU_MAX (single-objective log EI family)
 
 
+# ---- construction shared by QNEI and QSoboNEI (their prune and incumbent rules differ) ----
+def _baseline_rows(X_train_raw, X_baseline_raw) -> np.ndarray:
+    """Baseline rows -> training rows (first exact match of the transformed inputs)."""
+    first = {}
+    for i, row in enumerate(map(tuple, np.asarray(X_train_raw, dtype=np.float64))):
+        first.setdefault(row, i)
+    try:
+        base_rows = np.array([first[tuple(r)] for r in np.asarray(X_baseline_raw, dtype=np.float64)], dtype=np.int64)
+    except KeyError as e:
+        raise ValueError("qNEI: every baseline point must be a training point of the model") from e
+    if base_rows.shape[0] == 0:
+        raise ValueError("qNEI needs a non-empty baseline")
+    return base_rows
+
+
+def _train_posterior(gp: GPBatch):
+    """Joint posterior per output at the training inputs, shared by prune and baseline:
+    (mu_train m x n, A = L^-1 K, Sig m x n x n in original units, ys2 = s^2)."""
+    K = gp.kernel_train(noise=False)                                    # m x n x n
+    mu_t = ops.gemm(K, gp.alpha.unsqueeze(-1))[..., 0]
+    mu_train = gp.ym[:, None] + gp.ys[:, None] * (gp.const[:, None] + mu_t)
+    A = ops.gemm(gp.Linv, K)                                            # L^-1 K
+    Sig = ops.gemm(A, A, transA=True, alpha=-1.0, beta=1.0, out=K)      # K - A^T A (in place)
+    ys2 = (gp.ys ** 2).contiguous()
+    ops.scale_batched(Sig, ys2)
+    return mu_train, A, Sig, ys2
+
+
+def _baseline_operator(gp: GPBatch, A, idx, L_base, Zb, ys2) -> torch.Tensor:
+    """M = [L^-1; G; H^T; alpha^T] per output, G = s^2 L_base^-1 (P - A_b^T L^-1), H = G^T Z_base,
+    over the baseline rows idx with root L_base and base samples Zb (m x nb x S)."""
+    n, (m, nb, S_) = gp.n, Zb.shape
+    Rr = n + nb + S_ + 1
+    M = torch.empty(m, Rr, n, dtype=torch.float64, device=gp.device)
+    M[:, :n].copy_(gp.Linv)
+    E = ops.gemm(A[:, :, idx].contiguous(), gp.Linv, transA=True, alpha=-1.0)
+    ops.add_selection(E, idx.to(torch.int32), None)
+    ops.scale_batched(E, ys2)
+    ops.trsm(L_base, E)
+    M[:, n:n + nb].copy_(E)
+    ops.gemm_into(M[:, n + nb:n + nb + S_], Zb, E, transA=True)
+    M[:, Rr - 1].copy_(gp.alpha)
+    return M
+
+
 class _NeiAcqf(_BoxHviAcqf):
     """Evaluation side of the single-objective improvement acquisitions (QNEI, QLogNEI,
     QLogEI): the general chain at one output with the improvement scan of nei_scan.hip
     between the joint samples and their adjoint (evr_qnei_eval) — no cells, no subsets.
-    Subclasses set gp, dev, S, M, nb and the incumbent(s) ``best`` and call _finish.
+    Subclasses set gp, dev, S, M, nb, spec and the incumbent(s) ``best`` and call _finish.
     Pending points ([upstream] concatenate_pending_points) join every candidate's joint
     batch; the graph-captured native plan does not cover these acquisitions (the optimiser
-    drives them through eval_host)."""
+    drives them through eval_host).
+
+    This class is also the one evaluation side of every acquisition behind that chain
+    (_SoboAcqf, _RewardAcqf): they override the five hooks below — the scan's struct, the
+    ops.*_eval to call, the evr_qn_general, the torch class and the autograd Function."""
 
     @property
     def supports_plan(self) -> bool:
         return False
 
-    def _finish(self, obj_a: float, obj_b: float, no_h: bool, log: bool, tau_relu: float, tau_max: float,
-                X_pending_raw):
+    def _set_affine(self, obj_a: float, obj_b: float):
+        """The one affine objective g = a y + b of the single-output classes."""
+        self.a, self.b = float(obj_a), float(obj_b)
+        self.spec = ops.GeneralSpec(1, [(0, ops.OBJ_AFFINE, self.a, self.b)])
+
+    def _chain_struct(self):
+        return ops.nei_struct(self.log_acqf, self.tau_relu, self.tau_max, self.best)
+
+    def _chain_eval(self):
+        return ops.qnei_eval
+
+    def _g(self, qq: int):
+        """evr_qn_general of a joint batch of qq points: the objective of the spec, q and zq."""
+        return self.spec.struct(qq, self._zq(qq))
+
+    def _torch_new(self, state, model, keep):
+        return torch.classes.everest_amd.QneiAcq(state, model, self.log_acqf, self.tau_relu, self.tau_max, self.best,
+                                                 self.a, self.b, keep)
+
+    def _function(self):
+        from .torch_ops import QneiFunction
+        return QneiFunction
+
+    def _finish(self, m: int, no_h: bool, log: bool, tau_relu: float, tau_max: float, X_pending_raw):
         gp = self.gp
         f64 = dict(dtype=torch.float64, device=self.dev)
         if log and not (tau_relu > 0 and tau_max > 0):
             raise ValueError("tau_relu and tau_max must be positive")
-        self.m, self.n, self.nk = 1, gp.n, gp.n
-        self.a, self.b = float(obj_a), float(obj_b)
+        self.m, self.n, self.nk = m, gp.n, gp.n
         self.log_acqf = bool(log)      # log values may be negative: optimize_acqf uses initialize_q_batch
         self.tau_relu, self.tau_max = float(tau_relu), float(tau_max)
-        self.spec = ops.GeneralSpec(1, [(0, ops.OBJ_AFFINE, self.a, self.b)])
         self.X_pending = None
         if X_pending_raw is not None and np.asarray(X_pending_raw).shape[0] > 0:
             self.X_pending = torch.as_tensor(np.asarray(X_pending_raw, dtype=np.float64).reshape(-1, gp.d), **f64)
         self.n_pending = 0 if self.X_pending is None else int(self.X_pending.shape[0])
         self.Xk = gp.Xn
         self.Rr = gp.n + self.nb + (0 if no_h else self.S) + 1
-        self.state = ops.model_state(gp.n, self.nb, self.S, gp.const, gp.ym, gp.ys, gp.kxx, no_h=no_h)
+        self.state = ops.model_state(gp.n, self.nb, self.S, gp.const, gp.ym, gp.ys, gp.kxx, no_h=no_h, m=m)
         self._lo_c = gp.lo.to(torch.float64).contiguous()
         self._scale_c = gp.inv_range.to(torch.float64).contiguous()
         self.model = _native.EvrQnehviModel(n=gp.n, d=gp.d, kind=gp.kind, Xn=self.Xk.data_ptr(),
                                             lengthscales=gp.ls.data_ptr(), shift=self._lo_c.data_ptr(),
                                             scale=self._scale_c.data_ptr(), M=self.M.data_ptr())
         self.best = self.best.to(**f64).reshape(-1).contiguous()
-        self.nei = ops.nei_struct(log, tau_relu, tau_max, self.best)
+        self.chain = self._chain_struct()
         self._zq_cache = {}
         self._plans = {}
         torch.cuda.synchronize(self.dev)
@@ -1032,30 +1101,29 @@ class _NeiAcqf(_BoxHviAcqf):
         return X
 
     def _general(self, X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
-        """X: b x q x d -> (acq (b), dX b x q x d | None) through evr_qnei_eval."""
+        """X: b x q x d -> (acq (b), dX b x q x d | None) through the chain's evr_q*_eval."""
         b, q, d = X.shape
         X = self._joint(X)
         qq = X.shape[1]
-        g = self.spec.struct(qq, self._zq(qq))
-        acq, dX = ops.qnei_eval(self.state, g, self.model, self.nei, X.reshape(b * qq, d).contiguous(), backward,
-                                gout)
+        acq, dX = self._chain_eval()(self.state, self._g(qq), self.model, self.chain,
+                                     X.reshape(b * qq, d).contiguous(), backward, gout)
         if dX is not None:
             dX = dX.view(b, qq, d)[:, :q].contiguous()
         return acq, dX
 
     def _torch_acq(self, q: int, fast: bool = False):
-        """The torch.classes.everest_amd.QneiAcq behind torch.ops.everest_amd.qnei_*."""
+        """The torch.classes.everest_amd.Q*Acq behind the chain's torch operators (torch_ops.cpp):
+        owns copies of the state / model structs and references to every device tensor they
+        point into."""
         from . import torch_ops
 
         torch_ops.load()
-        acq = self.__dict__.get("_torch_nei")
+        acq = self.__dict__.get("_torch_chain")
         if acq is None:
             def raw(st):
                 return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8)
-            acq = torch.classes.everest_amd.QneiAcq(raw(self.state), raw(self.model), self.log_acqf, self.tau_relu,
-                                                    self.tau_max, self.best, self.a, self.b, self._device_tensors())
-            self._torch_nei = acq
-        done = self.__dict__.setdefault("_torch_nei_q", set())
+            acq = self._torch_chain = self._torch_new(raw(self.state), raw(self.model), self._device_tensors())
+        done = self.__dict__.setdefault("_torch_chain_q", set())
         if q not in done:
             acq.set_samples(int(q), self._zq(q))
             done.add(q)
@@ -1063,11 +1131,9 @@ class _NeiAcqf(_BoxHviAcqf):
 
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
         """X (b x q x d, or b x d for q = 1) -> acq (b), differentiable through the device
-        backward (torch.ops.everest_amd.qnei_forward / qnei_forward_backward)."""
-        from .torch_ops import QneiFunction
-
+        backward (the chain's torch.ops.everest_amd.q*_forward / q*_forward_backward)."""
         X3 = self._joint(self._split(X)[0]).contiguous()
-        return QneiFunction.apply(X3, self._torch_acq(X3.shape[1]))
+        return self._function().apply(X3, self._torch_acq(X3.shape[1]))
 
 
 class QNEI(_NeiAcqf):
@@ -1102,29 +1168,12 @@ class QNEI(_NeiAcqf):
         dev = gp.device
         self.gp, self.dev, self.S = gp, dev, int(S)
         self.sampler_seed = int(sampler_seed)
-        n, S_ = gp.n, self.S
+        S_ = self.S
         f64 = dict(dtype=torch.float64, device=dev)
         a_t = torch.tensor([float(obj_a)], **f64)
         b_t = torch.tensor([float(obj_b)], **f64)
-        # baseline rows -> training rows (first exact match of the transformed inputs)
-        first = {}
-        for i, row in enumerate(map(tuple, np.asarray(X_train_raw, dtype=np.float64))):
-            first.setdefault(row, i)
-        try:
-            base_rows = np.array([first[tuple(r)] for r in np.asarray(X_baseline_raw, dtype=np.float64)],
-                                 dtype=np.int64)
-        except KeyError as e:
-            raise ValueError("qNEI: every baseline point must be a training point of the model") from e
-        if base_rows.shape[0] == 0:
-            raise ValueError("qNEI needs a non-empty baseline")
-        # joint posterior at the training inputs, shared by prune and baseline
-        K = gp.kernel_train(noise=False)                                    # 1 x n x n
-        mu_t = ops.gemm(K, gp.alpha.unsqueeze(-1))[..., 0]
-        mu_train = gp.ym[:, None] + gp.ys[:, None] * (gp.const[:, None] + mu_t)
-        A = ops.gemm(gp.Linv, K)                                            # L^-1 K
-        Sig = ops.gemm(A, A, transA=True, alpha=-1.0, beta=1.0, out=K)      # K - A^T A (in place)
-        ys2 = (gp.ys ** 2).contiguous()
-        ops.scale_batched(Sig, ys2)
+        base_rows = _baseline_rows(X_train_raw, X_baseline_raw)
+        mu_train, A, Sig, ys2 = _train_posterior(gp)
         self.prune_counts = None
         if prune_baseline:
             cand = torch.as_tensor(base_rows, device=dev)
@@ -1149,19 +1198,9 @@ class QNEI(_NeiAcqf):
         self._Zb = Zb
         Ob = ops.objective_affine(ops.gemm(self.L_base, Zb), mu_train[:, idx].contiguous(), a_t, b_t)
         self.best = Ob[0].amax(0)                                                       # S
-        # operator M = [L^-1; G; H^T; alpha^T], G = s^2 L_base^-1 (P - A_b^T L^-1), H = G^T Z_base
-        Rr = n + nb + S_ + 1
-        M = torch.empty(1, Rr, n, **f64)
-        M[:, :n].copy_(gp.Linv)
-        E = ops.gemm(A[:, :, idx].contiguous(), gp.Linv, transA=True, alpha=-1.0)
-        ops.add_selection(E, idx.to(torch.int32), None)
-        ops.scale_batched(E, ys2)
-        ops.trsm(self.L_base, E)
-        M[:, n:n + nb].copy_(E)
-        ops.gemm_into(M[:, n + nb:n + nb + S_], Zb, E, transA=True)
-        M[:, Rr - 1].copy_(gp.alpha)
-        self.M = M
-        self._finish(obj_a, obj_b, False, self._LOG, tau_relu, tau_max, X_pending_raw)
+        self.M = _baseline_operator(gp, A, idx, self.L_base, Zb, ys2)
+        self._set_affine(obj_a, obj_b)
+        self._finish(1, False, self._LOG, tau_relu, tau_max, X_pending_raw)
 
     def z_base_host(self) -> torch.Tensor:
         """The baseline base samples (S x nb x 1, host), the oracle's layout."""
@@ -1200,7 +1239,8 @@ class QLogEI(_NeiAcqf):
         self.best_f = float((float(obj_a) * mean[0] + float(obj_b)).max().item())
         self.best = torch.tensor([self.best_f], dtype=torch.float64, device=self.dev)
         self.M = gp.M
-        self._finish(obj_a, obj_b, True, log, tau_relu, tau_max, X_pending_raw)
+        self._set_affine(obj_a, obj_b)
+        self._finish(1, True, log, tau_relu, tau_max, X_pending_raw)
 
     def z_base_host(self) -> None:
         """No baseline draw (plain joint sampling)."""
@@ -1236,8 +1276,8 @@ class _SoboAcqf(_NeiAcqf):
     joint samples and their adjoint (evr_qsobo_eval) — [upstream]
     SampleReducingMCAcquisitionFunction._apply_constraints weighs every (sample, point) before
     the reduction over q, so the hypervolume chain's q-subset weighting does not apply.
-    Subclasses set gp, dev, S, M, nb, spec and the incumbent(s) ``best`` and call _finish_sobo.
-    The spec decides the scan: an ops.SoboSpec runs evr_qsobo_eval, an ops.ParegoSpec (the
+    Subclasses set gp, dev, S, M, nb, spec and the incumbent(s) ``best`` and call _finish; the
+    evaluation is _NeiAcqf's through the hooks below.  The spec decides the scan: an ops.SoboSpec runs evr_qsobo_eval, an ops.ParegoSpec (the
     QParego* classes) evr_qparego_eval with the augmented Chebyshev scan of parego_scan.hip;
     construction, incumbents and pruning only use the spec's utility / feasible.
 
@@ -1256,79 +1296,32 @@ class _SoboAcqf(_NeiAcqf):
         if gp.mask is not None:
             raise NotImplementedError(f"{name}: outputs fitted on different row sets are not supported")
 
-    def _finish_sobo(self, no_h: bool, log: bool, tau_relu: float, tau_max: float, X_pending_raw):
-        gp = self.gp
-        f64 = dict(dtype=torch.float64, device=self.dev)
-        if log and not (tau_relu > 0 and tau_max > 0):
-            raise ValueError("tau_relu and tau_max must be positive")
-        self.m, self.n, self.nk = gp.B, gp.n, gp.n
-        self.log_acqf = bool(log)
-        self.tau_relu, self.tau_max = float(tau_relu), float(tau_max)
-        self.X_pending = None
-        if X_pending_raw is not None and np.asarray(X_pending_raw).shape[0] > 0:
-            self.X_pending = torch.as_tensor(np.asarray(X_pending_raw, dtype=np.float64).reshape(-1, gp.d), **f64)
-        self.n_pending = 0 if self.X_pending is None else int(self.X_pending.shape[0])
-        self.Xk = gp.Xn
-        self.Rr = gp.n + self.nb + (0 if no_h else self.S) + 1
-        self.state = ops.model_state(gp.n, self.nb, self.S, gp.const, gp.ym, gp.ys, gp.kxx, no_h=no_h, m=gp.B)
-        self._lo_c = gp.lo.to(torch.float64).contiguous()
-        self._scale_c = gp.inv_range.to(torch.float64).contiguous()
-        self.model = _native.EvrQnehviModel(n=gp.n, d=gp.d, kind=gp.kind, Xn=self.Xk.data_ptr(),
-                                            lengthscales=gp.ls.data_ptr(), shift=self._lo_c.data_ptr(),
-                                            scale=self._scale_c.data_ptr(), M=self.M.data_ptr())
-        self.best = self.best.to(**f64).reshape(-1).contiguous()
-        self.sb = self.spec.struct(log, tau_relu, tau_max, self.best)
-        self._zq_cache = {}
-        self._plans = {}
-        torch.cuda.synchronize(self.dev)
+    def _chain_struct(self):
+        return self.spec.struct(self.log_acqf, self.tau_relu, self.tau_max, self.best)
 
-    def _general(self, X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
-        """X: b x q x d -> (acq (b), dX b x q x d | None) through evr_qsobo_eval (evr_qparego_eval
-        for an ops.ParegoSpec)."""
-        b, q, d = X.shape
-        X = self._joint(X)
-        qq = X.shape[1]
+    def _chain_eval(self):
+        return ops.qparego_eval if self._parego else ops.qsobo_eval
+
+    def _g(self, qq: int):
+        """q and zq only: the scans over several outputs carry their own tables."""
         g = _native.EvrQnGeneral()
         g.q, g.zq = int(qq), self._zq(qq).data_ptr()
-        ev = ops.qparego_eval if self._parego else ops.qsobo_eval
-        acq, dX = ev(self.state, g, self.model, self.sb, X.reshape(b * qq, d).contiguous(), backward, gout)
-        if dX is not None:
-            dX = dX.view(b, qq, d)[:, :q].contiguous()
-        return acq, dX
+        return g
 
-    def _torch_acq(self, q: int, fast: bool = False):
-        """The torch.classes.everest_amd.QsoboAcq behind torch.ops.everest_amd.qsobo_* (QparegoAcq
-        and qparego_* for an ops.ParegoSpec)."""
-        from . import torch_ops
+    def _tables(self):
+        """The spec's term (n x 6) and constraint (n x 4) rows as the torch classes take them."""
+        return (torch.tensor(self.spec.terms, dtype=torch.float64).reshape(-1, 6),
+                torch.tensor(self.spec.constraints, dtype=torch.float64).reshape(-1, 4))
 
-        torch_ops.load()
-        acq = self.__dict__.get("_torch_sobo")
-        if acq is None:
-            def raw(st):
-                return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8)
-            terms = torch.tensor(self.spec.terms, dtype=torch.float64).reshape(-1, 6)
-            cons = torch.tensor(self.spec.constraints, dtype=torch.float64).reshape(-1, 4)
-            cls = torch.classes.everest_amd
-            if self._parego:
-                acq = cls.QparegoAcq(raw(self.state), raw(self.model), self.log_acqf, self.tau_relu, self.tau_max,
-                                     self.best, self.spec.alpha, terms, cons, self._device_tensors())
-            else:
-                acq = cls.QsoboAcq(raw(self.state), raw(self.model), self.log_acqf, self.tau_relu, self.tau_max,
-                                   self.best, terms, cons, self._device_tensors())
-            self._torch_sobo = acq
-        done = self.__dict__.setdefault("_torch_sobo_q", set())
-        if q not in done:
-            acq.set_samples(int(q), self._zq(q))
-            done.add(q)
-        return acq
+    def _torch_new(self, state, model, keep):
+        head = (state, model, self.log_acqf, self.tau_relu, self.tau_max, self.best)
+        if self._parego:
+            return torch.classes.everest_amd.QparegoAcq(*head, self.spec.alpha, *self._tables(), keep)
+        return torch.classes.everest_amd.QsoboAcq(*head, *self._tables(), keep)
 
-    def __call__(self, X: torch.Tensor) -> torch.Tensor:
-        """X (b x q x d, or b x d for q = 1) -> acq (b), differentiable through the device
-        backward (torch.ops.everest_amd.qsobo_forward / qsobo_forward_backward)."""
+    def _function(self):
         from .torch_ops import QparegoFunction, QsoboFunction
-
-        X3 = self._joint(self._split(X)[0]).contiguous()
-        return (QparegoFunction if self._parego else QsoboFunction).apply(X3, self._torch_acq(X3.shape[1]))
+        return QparegoFunction if self._parego else QsoboFunction
 
 
 class QSoboNEI(_SoboAcqf):
@@ -1363,26 +1356,10 @@ class QSoboNEI(_SoboAcqf):
         dev = gp.device
         self.gp, self.dev, self.S, self.spec = gp, dev, int(S), spec
         self.sampler_seed = int(sampler_seed)
-        n, S_, m = gp.n, self.S, gp.B
+        S_, m = self.S, gp.B
         f64 = dict(dtype=torch.float64, device=dev)
-        first = {}
-        for i, row in enumerate(map(tuple, np.asarray(X_train_raw, dtype=np.float64))):
-            first.setdefault(row, i)
-        try:
-            base_rows = np.array([first[tuple(r)] for r in np.asarray(X_baseline_raw, dtype=np.float64)],
-                                 dtype=np.int64)
-        except KeyError as e:
-            raise ValueError("qNEI: every baseline point must be a training point of the model") from e
-        if base_rows.shape[0] == 0:
-            raise ValueError("qNEI needs a non-empty baseline")
-        # joint posterior per output at the training inputs, shared by prune and baseline
-        K = gp.kernel_train(noise=False)                                    # m x n x n
-        mu_t = ops.gemm(K, gp.alpha.unsqueeze(-1))[..., 0]
-        mu_train = gp.ym[:, None] + gp.ys[:, None] * (gp.const[:, None] + mu_t)
-        A = ops.gemm(gp.Linv, K)                                            # L^-1 K
-        Sig = ops.gemm(A, A, transA=True, alpha=-1.0, beta=1.0, out=K)      # K - A^T A (in place)
-        ys2 = (gp.ys ** 2).contiguous()
-        ops.scale_batched(Sig, ys2)
+        base_rows = _baseline_rows(X_train_raw, X_baseline_raw)
+        mu_train, A, Sig, ys2 = _train_posterior(gp)
         var_train = torch.diagonal(Sig, dim1=-2, dim2=-1)                   # m x n
 
         def draws(L, Z, rows):
@@ -1415,19 +1392,8 @@ class QSoboNEI(_SoboAcqf):
         Yb = draws(self.L_base, Zb, idx)                                                # S x nb x m
         self.best = _best_feasible(spec.utility(Yb), spec.feasible(Yb),
                                    lambda: _lower_bound(spec, mu_train[:, idx], var_train[:, idx]))
-        # operator M = [L^-1; G; H^T; alpha^T] per output, G = s^2 L_base^-1 (P - A_b^T L^-1), H = G^T Z_base
-        Rr = n + nb + S_ + 1
-        M = torch.empty(m, Rr, n, **f64)
-        M[:, :n].copy_(gp.Linv)
-        E = ops.gemm(A[:, :, idx].contiguous(), gp.Linv, transA=True, alpha=-1.0)
-        ops.add_selection(E, idx.to(torch.int32), None)
-        ops.scale_batched(E, ys2)
-        ops.trsm(self.L_base, E)
-        M[:, n:n + nb].copy_(E)
-        ops.gemm_into(M[:, n + nb:n + nb + S_], Zb, E, transA=True)
-        M[:, Rr - 1].copy_(gp.alpha)
-        self.M = M
-        self._finish_sobo(False, self._LOG, tau_relu, tau_max, X_pending_raw)
+        self.M = _baseline_operator(gp, A, idx, self.L_base, Zb, ys2)
+        self._finish(m, False, self._LOG, tau_relu, tau_max, X_pending_raw)
 
     def z_base_host(self) -> torch.Tensor:
         """The baseline base samples (S x nb x m, host), the oracle's layout."""
@@ -1466,7 +1432,7 @@ class QSoboLogEI(_SoboAcqf):
                                    lambda: _lower_bound(spec, mean, var)).reshape(1)
         self.best_f = float(self.best.item())
         self.M = gp.M
-        self._finish_sobo(True, log, tau_relu, tau_max, X_pending_raw)
+        self._finish(gp.B, True, log, tau_relu, tau_max, X_pending_raw)
 
     def z_base_host(self) -> None:
         """No baseline draw (plain joint sampling)."""
@@ -1513,9 +1479,22 @@ class _RewardAcqf(_SoboAcqf):
         else:
             self.best = torch.zeros(1, dtype=torch.float64, device=self.dev)    # not read
         self.M = gp.M
-        self._finish_sobo(True, False, TAU_RELU, TAU_MAX_SO, X_pending_raw)
+        self._finish(gp.B, True, False, TAU_RELU, TAU_MAX_SO, X_pending_raw)
         self.best_f = float(self.best.item()) if self._MODE == ops.REWARD_PI else None
-        self.rw = ops.reward_struct(spec, self._MODE, self.beta, self.tau, self.best, self.infeasible_cost)
+
+    def _chain_struct(self):
+        return ops.reward_struct(self.spec, self._MODE, self.beta, self.tau, self.best, self.infeasible_cost)
+
+    def _chain_eval(self):
+        return ops.qreward_eval
+
+    def _torch_new(self, state, model, keep):
+        return torch.classes.everest_amd.QrewardAcq(state, model, int(self._MODE), float(self.chain.ucb_scale),
+                                                    self.tau, self.infeasible_cost, self.best, *self._tables(), keep)
+
+    def _function(self):
+        from .torch_ops import QrewardFunction
+        return QrewardFunction
 
     def z_base_host(self) -> None:
         """No baseline draw (plain joint sampling)."""
@@ -1523,48 +1502,6 @@ class _RewardAcqf(_SoboAcqf):
 
     def _draw_zq(self, q: int) -> torch.Tensor:
         return ops.sobol_normal(self.S, q * self.m, self.sampler_seed, self.dev)
-
-    def _general(self, X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
-        """X: b x q x d -> (acq (b), dX b x q x d | None) through evr_qreward_eval."""
-        b, q, d = X.shape
-        X = self._joint(X)
-        qq = X.shape[1]
-        g = _native.EvrQnGeneral()
-        g.q, g.zq = int(qq), self._zq(qq).data_ptr()
-        acq, dX = ops.qreward_eval(self.state, g, self.model, self.rw, X.reshape(b * qq, d).contiguous(), backward,
-                                   gout)
-        if dX is not None:
-            dX = dX.view(b, qq, d)[:, :q].contiguous()
-        return acq, dX
-
-    def _torch_acq(self, q: int, fast: bool = False):
-        """The torch.classes.everest_amd.QrewardAcq behind torch.ops.everest_amd.qreward_*."""
-        from . import torch_ops
-
-        torch_ops.load()
-        acq = self.__dict__.get("_torch_reward")
-        if acq is None:
-            def raw(st):
-                return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8)
-            terms = torch.tensor(self.spec.terms, dtype=torch.float64).reshape(-1, 6)
-            cons = torch.tensor(self.spec.constraints, dtype=torch.float64).reshape(-1, 4)
-            acq = torch.classes.everest_amd.QrewardAcq(raw(self.state), raw(self.model), int(self._MODE),
-                                                       float(self.rw.ucb_scale), self.tau, self.infeasible_cost,
-                                                       self.best, terms, cons, self._device_tensors())
-            self._torch_reward = acq
-        done = self.__dict__.setdefault("_torch_reward_q", set())
-        if q not in done:
-            acq.set_samples(int(q), self._zq(q))
-            done.add(q)
-        return acq
-
-    def __call__(self, X: torch.Tensor) -> torch.Tensor:
-        """X (b x q x d, or b x d for q = 1) -> acq (b), differentiable through the device
-        backward (torch.ops.everest_amd.qreward_forward / qreward_forward_backward)."""
-        from .torch_ops import QrewardFunction
-
-        X3 = self._joint(self._split(X)[0]).contiguous()
-        return QrewardFunction.apply(X3, self._torch_acq(X3.shape[1]))
 
 
 class QSoboSR(_RewardAcqf):

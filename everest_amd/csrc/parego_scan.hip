@@ -167,38 +167,14 @@ __global__ __launch_bounds__(NS_THREADS) void parego_scan(int S, int b, PgTab t,
 }
 
 static int pg_params(const evr_parego* pg, int m_model, PgTab* t) {
-  EVR_CHECK(pg && m_model >= 1 && m_model <= QG_MAXM && pg->n_term >= 2 && pg->n_term <= EVR_SOBO_MAX_TERMS &&
-                pg->n_con >= 0 && pg->n_con <= QG_MAXC && pg->term_out && pg->term_kind && pg->term_p0 &&
-                pg->term_p1 && pg->term_a && pg->term_b &&
-                (pg->n_con == 0 || (pg->con_out && pg->con_sign && pg->con_thr && pg->con_eta)),
-            "parego_scan: bad term / constraint description (terms 2..%d, constraints 0..%d, outputs 1..%d)",
-            EVR_SOBO_MAX_TERMS, QG_MAXC, QG_MAXM);
-  EVR_CHECK(pg->alpha >= 0.0, "parego_scan: alpha = %g is negative", pg->alpha);
   std::memset(t, 0, sizeof(*t));
-  t->o.m = m_model;
-  t->o.mo = pg->n_term;
-  t->o.nc = pg->n_con;
+  if (int rc = sb_fill("parego_scan", pg, pg && pg->term_a && pg->term_b, m_model, 2, false, &t->o)) return rc;
+  EVR_CHECK(pg->alpha >= 0.0, "parego_scan: alpha = %g is negative", pg->alpha);
   t->alpha = pg->alpha;
   for (int k = 0; k < pg->n_term; ++k) {
-    EVR_CHECK(pg->term_out[k] >= 0 && pg->term_out[k] < m_model, "parego_scan: term %d reads output %d of %d", k,
-              pg->term_out[k], m_model);
-    EVR_CHECK(pg->term_kind[k] == EVR_OBJ_AFFINE || pg->term_kind[k] == EVR_OBJ_CLOSE_TO_TARGET,
-              "parego_scan: term kind %d (affine and close-to-target only)", pg->term_kind[k]);
     EVR_CHECK(pg->term_a[k] > 0.0, "parego_scan: term %d has scale A = %g (must be positive)", k, pg->term_a[k]);
-    t->o.oo[k] = pg->term_out[k];
-    t->o.ok[k] = pg->term_kind[k];
-    t->o.p0[k] = pg->term_p0[k];
-    t->o.p1[k] = pg->term_p1[k];
     t->A[k] = pg->term_a[k];
     t->B[k] = pg->term_b[k];
-  }
-  for (int e = 0; e < pg->n_con; ++e) {
-    EVR_CHECK(pg->con_out[e] >= 0 && pg->con_out[e] < m_model && pg->con_eta[e] > 0.0,
-              "parego_scan: constraint %d (output %d, eta %g)", e, pg->con_out[e], pg->con_eta[e]);
-    t->o.co[e] = pg->con_out[e];
-    t->o.cs[e] = pg->con_sign[e];
-    t->o.ct[e] = pg->con_thr[e];
-    t->o.ce[e] = pg->con_eta[e];
   }
   return 0;
 }

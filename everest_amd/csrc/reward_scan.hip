@@ -271,46 +271,11 @@ __global__ __launch_bounds__(NS_THREADS) void reward_scan(int S, int b, SbTab t,
   }
 }
 
-static int rw_params(const evr_reward* rw, int m_model, SbTab* t) {
-  EVR_CHECK(rw && m_model >= 1 && m_model <= QG_MAXM && rw->n_term >= 1 && rw->n_term <= EVR_SOBO_MAX_TERMS &&
-                rw->n_con >= 0 && rw->n_con <= QG_MAXC && rw->term_out && rw->term_kind && rw->term_w &&
-                rw->term_p0 && rw->term_p1 && rw->term_p2 &&
-                (rw->n_con == 0 || (rw->con_out && rw->con_sign && rw->con_thr && rw->con_eta)),
-            "reward_scan: bad term / constraint description (terms 1..%d, constraints 0..%d, outputs 1..%d)",
-            EVR_SOBO_MAX_TERMS, QG_MAXC, QG_MAXM);
-  std::memset(t, 0, sizeof(*t));
-  t->o.m = m_model;
-  t->o.mo = rw->n_term;
-  t->o.nc = rw->n_con;
-  for (int k = 0; k < rw->n_term; ++k) {
-    EVR_CHECK(rw->term_out[k] >= 0 && rw->term_out[k] < m_model, "reward_scan: term %d reads output %d of %d", k,
-              rw->term_out[k], m_model);
-    EVR_CHECK(rw->term_kind[k] == EVR_OBJ_AFFINE || rw->term_kind[k] == EVR_OBJ_CLOSE_TO_TARGET ||
-                  rw->term_kind[k] == EVR_OBJ_SIGMOID || rw->term_kind[k] == EVR_OBJ_TARGET,
-              "reward_scan: term kind %d", rw->term_kind[k]);
-    t->o.oo[k] = rw->term_out[k];
-    t->o.ok[k] = rw->term_kind[k];
-    t->o.p0[k] = rw->term_p0[k];
-    t->o.p1[k] = rw->term_p1[k];
-    t->w[k] = rw->term_w[k];
-    t->p2[k] = rw->term_p2[k];
-  }
-  for (int e = 0; e < rw->n_con; ++e) {
-    EVR_CHECK(rw->con_out[e] >= 0 && rw->con_out[e] < m_model && rw->con_eta[e] > 0.0,
-              "reward_scan: constraint %d (output %d, eta %g)", e, rw->con_out[e], rw->con_eta[e]);
-    t->o.co[e] = rw->con_out[e];
-    t->o.cs[e] = rw->con_sign[e];
-    t->o.ct[e] = rw->con_thr[e];
-    t->o.ce[e] = rw->con_eta[e];
-  }
-  return 0;
-}
-
 int reward_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_reward* rw, const double* Y,
                        const int* flags, const double* gout, double* acq, double* dY) {
   EVR_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "reward_scan: q = %d outside 1..%d", q, EVR_QNG_MAX_Q);
   SbTab t;
-  if (int rc = rw_params(rw, m_model, &t)) return rc;
+  if (int rc = sb_tab("reward_scan", rw, m_model, &t)) return rc;
   const int mode = rw->mode;
   EVR_CHECK(mode == EVR_REWARD_SR || mode == EVR_REWARD_UCB || mode == EVR_REWARD_PI, "reward_scan: mode %d", mode);
   EVR_CHECK(S >= 1 && b >= 0 && Y && acq, "reward_scan: bad arguments (S >= 1)");

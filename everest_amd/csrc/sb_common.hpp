@@ -4,6 +4,7 @@
 // utility, as functions of their own: the summed log feasibilities of the q points, the reduction
 // over the q points of a (sample, candidate), and the constraint slopes of one output row.
 // sobo_scan.hip keeps its own fused copies of those three: its device code is unchanged.
+// Host side: the table check and copy of the three scans (sb_fill, sb_tab), reward_scan.hip's too.
 #pragma once
 #include "common.hpp"
 #include "ns_reduce.hpp"
@@ -127,6 +128,59 @@ __device__ __forceinline__ void sb_dfeas(const QgObj& o, int j, const double* __
       acc[i] += dl[i] * (LOG ? qg_dlog_fatmoid(x) : qg_sig(-x)) * sc;
     }
   }
+}
+
+// host: what the three scans' table builders share.  Checks the description p (evr_sobo,
+// evr_parego or evr_reward: the fields read here carry the same names) and copies m, the term
+// headers (out, kind, p0, p1) and the constraints into o; the caller adds its own term columns.
+// who: the caller's name for the messages; cols: whether the caller's own term columns are
+// there; min_terms: 1 (sum of terms) or 2 (Chebyshev); sig_kinds: whether the sigmoid and target
+// kinds are allowed beside affine and close-to-target.
+template <class P>
+static int sb_fill(const char* who, const P* p, bool cols, int m_model, int min_terms, bool sig_kinds, QgObj* o) {
+  EVR_CHECK(p && cols && m_model >= 1 && m_model <= QG_MAXM && p->n_term >= min_terms &&
+                p->n_term <= EVR_SOBO_MAX_TERMS && p->n_con >= 0 && p->n_con <= QG_MAXC && p->term_out &&
+                p->term_kind && p->term_p0 && p->term_p1 &&
+                (p->n_con == 0 || (p->con_out && p->con_sign && p->con_thr && p->con_eta)),
+            "%s: bad term / constraint description (terms %d..%d, constraints 0..%d, outputs 1..%d)", who, min_terms,
+            EVR_SOBO_MAX_TERMS, QG_MAXC, QG_MAXM);
+  o->m = m_model;
+  o->mo = p->n_term;
+  o->nc = p->n_con;
+  for (int k = 0; k < p->n_term; ++k) {
+    const int kind = p->term_kind[k];
+    EVR_CHECK(p->term_out[k] >= 0 && p->term_out[k] < m_model, "%s: term %d reads output %d of %d", who, k,
+              p->term_out[k], m_model);
+    EVR_CHECK(kind == EVR_OBJ_AFFINE || kind == EVR_OBJ_CLOSE_TO_TARGET ||
+                  (sig_kinds && (kind == EVR_OBJ_SIGMOID || kind == EVR_OBJ_TARGET)),
+              "%s: term kind %d%s", who, kind, sig_kinds ? "" : " (affine and close-to-target only)");
+    o->oo[k] = p->term_out[k];
+    o->ok[k] = kind;
+    o->p0[k] = p->term_p0[k];
+    o->p1[k] = p->term_p1[k];
+  }
+  for (int e = 0; e < p->n_con; ++e) {
+    EVR_CHECK(p->con_out[e] >= 0 && p->con_out[e] < m_model && p->con_eta[e] > 0.0,
+              "%s: constraint %d (output %d, eta %g)", who, e, p->con_out[e], p->con_eta[e]);
+    o->co[e] = p->con_out[e];
+    o->cs[e] = p->con_sign[e];
+    o->ct[e] = p->con_thr[e];
+    o->ce[e] = p->con_eta[e];
+  }
+  return 0;
+}
+
+// host: the table of a sum of terms (evr_sobo, evr_reward) — sb_fill plus the weights and the
+// third parameters
+template <class P>
+static int sb_tab(const char* who, const P* p, int m_model, SbTab* t) {
+  std::memset(t, 0, sizeof(*t));
+  if (int rc = sb_fill(who, p, p && p->term_w && p->term_p2, m_model, 1, true, &t->o)) return rc;
+  for (int k = 0; k < p->n_term; ++k) {
+    t->w[k] = p->term_w[k];
+    t->p2[k] = p->term_p2[k];
+  }
+  return 0;
 }
 
 // shared by the launchers: the q switch over the compiled instantiations

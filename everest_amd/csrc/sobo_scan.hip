@@ -198,46 +198,11 @@ __global__ __launch_bounds__(NS_THREADS) void sobo_scan(int S, int b, SbTab t, c
   }
 }
 
-static int sb_params(const evr_sobo* sb, int m_model, SbTab* t) {
-  EVR_CHECK(sb && m_model >= 1 && m_model <= QG_MAXM && sb->n_term >= 1 && sb->n_term <= EVR_SOBO_MAX_TERMS &&
-                sb->n_con >= 0 && sb->n_con <= QG_MAXC && sb->term_out && sb->term_kind && sb->term_w &&
-                sb->term_p0 && sb->term_p1 && sb->term_p2 &&
-                (sb->n_con == 0 || (sb->con_out && sb->con_sign && sb->con_thr && sb->con_eta)),
-            "sobo_scan: bad term / constraint description (terms 1..%d, constraints 0..%d, outputs 1..%d)",
-            EVR_SOBO_MAX_TERMS, QG_MAXC, QG_MAXM);
-  std::memset(t, 0, sizeof(*t));
-  t->o.m = m_model;
-  t->o.mo = sb->n_term;
-  t->o.nc = sb->n_con;
-  for (int k = 0; k < sb->n_term; ++k) {
-    EVR_CHECK(sb->term_out[k] >= 0 && sb->term_out[k] < m_model, "sobo_scan: term %d reads output %d of %d", k,
-              sb->term_out[k], m_model);
-    EVR_CHECK(sb->term_kind[k] == EVR_OBJ_AFFINE || sb->term_kind[k] == EVR_OBJ_CLOSE_TO_TARGET ||
-                  sb->term_kind[k] == EVR_OBJ_SIGMOID || sb->term_kind[k] == EVR_OBJ_TARGET,
-              "sobo_scan: term kind %d", sb->term_kind[k]);
-    t->o.oo[k] = sb->term_out[k];
-    t->o.ok[k] = sb->term_kind[k];
-    t->o.p0[k] = sb->term_p0[k];
-    t->o.p1[k] = sb->term_p1[k];
-    t->w[k] = sb->term_w[k];
-    t->p2[k] = sb->term_p2[k];
-  }
-  for (int e = 0; e < sb->n_con; ++e) {
-    EVR_CHECK(sb->con_out[e] >= 0 && sb->con_out[e] < m_model && sb->con_eta[e] > 0.0,
-              "sobo_scan: constraint %d (output %d, eta %g)", e, sb->con_out[e], sb->con_eta[e]);
-    t->o.co[e] = sb->con_out[e];
-    t->o.cs[e] = sb->con_sign[e];
-    t->o.ct[e] = sb->con_thr[e];
-    t->o.ce[e] = sb->con_eta[e];
-  }
-  return 0;
-}
-
 int sobo_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_sobo* sb, const double* Y,
                      const int* flags, const double* gout, double* acq, double* dY) {
   EVR_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "sobo_scan: q = %d outside 1..%d", q, EVR_QNG_MAX_Q);
   SbTab t;
-  if (int rc = sb_params(sb, m_model, &t)) return rc;
+  if (int rc = sb_tab("sobo_scan", sb, m_model, &t)) return rc;
   EVR_CHECK(S >= 1 && b >= 0 && Y && sb->best && acq && (sb->best_stride == 0 || sb->best_stride == 1),
             "sobo_scan: bad arguments (S >= 1, best_stride 0 or 1)");
   const bool log_mode = sb->log != 0;

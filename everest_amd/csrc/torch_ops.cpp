@@ -6,6 +6,11 @@
 // everest_amd/torch_ops.py).  Every op runs on torch's current HIP stream, allocates its
 // outputs and scratch with the torch caching allocator, checks device / dtype with
 // TORCH_CHECK (-> RuntimeError) and raises the C-ABI's evr_last_error() on failure.
+//
+// Structure: the dense ops, then QnehviAcq (the hypervolume chain with its plan cache), then
+// ChainAcq — the one host path of the single-objective acquisitions, whose four registered
+// classes (QneiAcq, QsoboAcq, QparegoAcq, QrewardAcq) add only their constructor arguments,
+// their parameter struct and the names of their two C functions.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -15,6 +20,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../../include/everest_amd.h"
@@ -39,6 +45,16 @@ at::Tensor scratch(int64_t doubles, const at::Tensor& like) {
 }
 
 const double* ptr(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr<double>() : nullptr; }
+
+// a C-ABI struct passed from Python as its bytes
+template <class T>
+T from_bytes(const char* cls, const at::Tensor& t, const char* what) {
+  TORCH_CHECK(t.device().is_cpu() && t.scalar_type() == at::kByte && t.numel() == (int64_t)sizeof(T), cls, ": ",
+              what, " must be a CPU uint8 tensor of ", sizeof(T), " bytes");
+  T v;
+  std::memcpy(&v, t.contiguous().data_ptr(), sizeof(T));
+  return v;
+}
 
 // K[b] = k(X1, X2; ls[b]) — evr_kernel_matrix
 at::Tensor kernel_matrix(const at::Tensor& X1_, const at::Tensor& X2_, const at::Tensor& ls_, int64_t kind) {
@@ -141,23 +157,14 @@ struct QnehviAcq : torch::CustomClassHolder {
   std::map<std::pair<int64_t, bool>, Plan> plans;
   int64_t n_evals = 0;
 
-  template <class T>
-  static T from_bytes(const at::Tensor& t, const char* what) {
-    TORCH_CHECK(t.device().is_cpu() && t.scalar_type() == at::kByte && t.numel() == (int64_t)sizeof(T),
-                "QnehviAcq: ", what, " must be a CPU uint8 tensor of ", sizeof(T), " bytes");
-    T v;
-    std::memcpy(&v, t.contiguous().data_ptr(), sizeof(T));
-    return v;
-  }
-
   bool log_scan = false;   // general path through evr_qlog_eval (qLogNEHVI / qLogEHVI)
 
   QnehviAcq(const at::Tensor& stm_b, const at::Tensor& sth_b, const at::Tensor& md_b, bool fast_, bool log_,
             std::vector<at::Tensor> keep_)
       : fast(fast_), keep(std::move(keep_)), log_scan(log_) {
-    stm = from_bytes<evr_qnehvi_state>(stm_b, "model-side state");
-    sth = from_bytes<evr_qnehvi_state>(sth_b, "scan-side state");
-    md = from_bytes<evr_qnehvi_model>(md_b, "model");
+    stm = from_bytes<evr_qnehvi_state>("QnehviAcq", stm_b, "model-side state");
+    sth = from_bytes<evr_qnehvi_state>("QnehviAcq", sth_b, "scan-side state");
+    md = from_bytes<evr_qnehvi_model>("QnehviAcq", md_b, "model");
     TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1, "QnehviAcq: inconsistent model");
   }
 
@@ -287,41 +294,56 @@ at::Tensor qnehvi_backward(const AcqPtr& acq, const at::Tensor& X, const at::Ten
 }
 
 // ---------------------------------------------------------------------------------------
-// The acquisition behind torch.ops.everest_amd.qnei_*: qNEI / qLogNEI / qLogEI through
-// evr_qnei_eval.  Owns copies of the state / model structs, the incumbent(s) and the base
-// samples per joint batch size, and references to the device tensors they point into.
+// The single-objective acquisitions: one scan each behind the same device chain (kernel
+// matrix, projection, q x q Gram / jittered Cholesky / joint samples, scan, analytic backward).
+// ChainAcq is their one host path.  It owns copies of the state / model structs, the scan's
+// parameter struct P, the incumbent(s), the base samples per joint batch size, and references
+// to the device tensors they point into.  WS / EV are the scan's evr_q*_workspace_doubles /
+// evr_q*_eval pair.
 // ---------------------------------------------------------------------------------------
-struct QneiAcq : torch::CustomClassHolder {
+template <class P>
+using ChainEval = int (*)(void*, const evr_qnehvi_state*, const evr_qn_general*, const evr_qnehvi_model*, const P*,
+                          int, const double*, const double*, double*, double*, double*);
+using ChainWork = long long (*)(const evr_qnehvi_state*, const evr_qn_general*, const evr_qnehvi_model*, int, int);
+
+template <class P, ChainWork WS, ChainEval<P> EV>
+struct ChainAcq : torch::CustomClassHolder {
+  const char *cls, *op;   // message prefixes: the registered class, the operator family
   evr_qnehvi_state stm{};
   evr_qnehvi_model md{};
-  evr_nei nei{};
-  int oo = 0, ok = EVR_OBJ_AFFINE;
-  double p0 = 1.0, p1 = 0.0;
+  evr_qn_general g0{};    // what the chain reads of g beside q and zq (QneiAcq: its one objective)
+  P par{};
   at::Tensor best;
   std::vector<at::Tensor> keep;
   std::map<int64_t, at::Tensor> zqs;
   int64_t n_evals = 0;
 
-  QneiAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
-          const at::Tensor& best_, double obj_a, double obj_b, std::vector<at::Tensor> keep_)
-      : p0(obj_a), p1(obj_b), keep(std::move(keep_)) {
-    stm = QnehviAcq::from_bytes<evr_qnehvi_state>(stm_b, "model-side state");
-    md = QnehviAcq::from_bytes<evr_qnehvi_model>(md_b, "model");
-    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m == 1,
-                "QneiAcq: inconsistent single-output model");
+  // per_sample: best may hold S per-sample incumbents (stride 1) beside one value (stride 0)
+  ChainAcq(const char* cls_, const char* op_, const at::Tensor& stm_b, const at::Tensor& md_b, const at::Tensor& best_,
+           bool per_sample, std::vector<at::Tensor> keep_)
+      : cls(cls_), op(op_), keep(std::move(keep_)) {
+    stm = from_bytes<evr_qnehvi_state>(cls, stm_b, "model-side state");
+    md = from_bytes<evr_qnehvi_model>(cls, md_b, "model");
+    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m >= 1, cls,
+                ": inconsistent model");
     best = dev64(best_, "best");
-    TORCH_CHECK(best.numel() == 1 || best.numel() == stm.S, "QneiAcq: best needs 1 or S values");
-    nei.log = log_ ? 1 : 0;
-    nei.tau_relu = tau_relu;
-    nei.tau_max = tau_max;
-    nei.best = best.data_ptr<double>();
-    nei.best_stride = best.numel() == 1 ? 0 : 1;
+    TORCH_CHECK(best.numel() == 1 || (per_sample && best.numel() == stm.S), cls,
+                per_sample ? ": best needs 1 or S values" : ": best needs one value");
+  }
+
+  // the improvement scans' shared head of P: log mode, temperatures, incumbent(s)
+  void improvement(bool log_, double tau_relu, double tau_max) {
+    par.log = log_ ? 1 : 0;
+    par.tau_relu = tau_relu;
+    par.tau_max = tau_max;
+    par.best = best.data_ptr<double>();
+    par.best_stride = best.numel() == 1 ? 0 : 1;
   }
 
   void set_samples(int64_t q, const at::Tensor& zq) {
-    TORCH_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "QneiAcq.set_samples: q = ", q, " outside 1..", EVR_QNG_MAX_Q);
+    TORCH_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, cls, ".set_samples: q = ", q, " outside 1..", EVR_QNG_MAX_Q);
     auto z = dev64(zq, "zq");
-    TORCH_CHECK(z.numel() == (int64_t)stm.S * q, "QneiAcq.set_samples: zq must be S x q");
+    TORCH_CHECK(z.numel() == (int64_t)stm.S * q * stm.m, cls, ".set_samples: zq must be S x q x m");
     zqs[q] = z;
   }
 
@@ -329,394 +351,181 @@ struct QneiAcq : torch::CustomClassHolder {
     auto X = dev64(X_, "X");
     c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
     hipStream_t s = cur_stream();
-    TORCH_CHECK(X.dim() == 3 && X.size(2) == md.d, "qnei: X must be b x q x d");
+    TORCH_CHECK(X.dim() == 3 && X.size(2) == md.d, op, ": X must be b x q x d");
     const int64_t b = X.size(0), q = X.size(1);
     auto it = zqs.find(q);
-    TORCH_CHECK(it != zqs.end(), "qnei: no base samples set for q = ", q);
-    evr_qn_general g{};
+    TORCH_CHECK(it != zqs.end(), op, ": no base samples set for q = ", q);
+    evr_qn_general g = g0;
     g.q = (int)q;
-    g.m_obj = 1;
-    g.obj_out = &oo;
-    g.obj_kind = &ok;
-    g.obj_p0 = &p0;
-    g.obj_p1 = &p1;
     g.zq = it->second.data_ptr<double>();
     auto acq = at::empty({b}, X.options());
     at::Tensor dX = backward ? at::empty_like(X) : at::Tensor();
     if (b == 0) return {acq, dX};
-    auto work = scratch(evr_qnei_workspace_doubles(&stm, &g, &md, (int)b, backward), X);
-    check(evr_qnei_eval(s, &stm, &g, &md, &nei, (int)b, X.data_ptr<double>(), nullptr, work.data_ptr<double>(),
-                        acq.data_ptr<double>(), backward ? dX.data_ptr<double>() : nullptr),
-          "qnei_eval");
+    auto work = scratch(WS(&stm, &g, &md, (int)b, backward), X);
+    check(EV(s, &stm, &g, &md, &par, (int)b, X.data_ptr<double>(), nullptr, work.data_ptr<double>(),
+             acq.data_ptr<double>(), backward ? dX.data_ptr<double>() : nullptr),
+          (std::string(op) + "_eval").c_str());
     ++n_evals;
     return {acq, dX};
   }
-
-  int64_t evals() const { return n_evals; }
 };
 
-using NeiPtr = c10::intrusive_ptr<QneiAcq>;
+// Owned term / constraint tables of the scans over several model outputs, parsed from
+// terms: n_term x 6 doubles (out, kind, then four columns the scan names) and
+// cons: n_con x 4 doubles (out, sign, thr, eta)
+struct ScanTables {
+  std::vector<int> to, tk, co;
+  std::vector<double> tc[4], cs, ct, ce;
 
-at::Tensor qnei_forward(const NeiPtr& acq, const at::Tensor& X) { return std::get<0>(acq->eval(X, false)); }
+  ScanTables(const char* cls, const at::Tensor& terms_, const at::Tensor& cons_, int64_t min_terms) {
+    auto T = terms_.to(at::kCPU, at::kDouble).contiguous();
+    auto C = cons_.to(at::kCPU, at::kDouble).contiguous();
+    TORCH_CHECK(T.dim() == 2 && T.size(1) == 6 && T.size(0) >= min_terms && T.size(0) <= EVR_SOBO_MAX_TERMS, cls,
+                ": terms must be n_term x 6, ", min_terms, "..", EVR_SOBO_MAX_TERMS, " rows");
+    TORCH_CHECK(C.numel() == 0 || (C.dim() == 2 && C.size(1) == 4), cls, ": constraints must be n_con x 4");
+    const double* t = T.data_ptr<double>();
+    for (int64_t k = 0; k < T.size(0); ++k, t += 6) {
+      to.push_back((int)t[0]);
+      tk.push_back((int)t[1]);
+      for (int j = 0; j < 4; ++j) tc[j].push_back(t[2 + j]);
+    }
+    const int64_t nc = C.numel() / 4;
+    const double* c = nc ? C.data_ptr<double>() : nullptr;
+    for (int64_t e = 0; e < nc; ++e, c += 4) {
+      co.push_back((int)c[0]);
+      cs.push_back(c[1]);
+      ct.push_back(c[2]);
+      ce.push_back(c[3]);
+    }
+  }
 
-std::tuple<at::Tensor, at::Tensor> qnei_forward_backward(const NeiPtr& acq, const at::Tensor& X) {
+  // the fields every scan struct names alike
+  template <class P>
+  void point(P& p) const {
+    p.n_term = (int)to.size();
+    p.term_out = to.data();
+    p.term_kind = tk.data();
+    p.n_con = (int)co.size();
+    p.con_out = co.empty() ? nullptr : co.data();
+    p.con_sign = co.empty() ? nullptr : cs.data();
+    p.con_thr = co.empty() ? nullptr : ct.data();
+    p.con_eta = co.empty() ? nullptr : ce.data();
+  }
+
+  // ... and the columns (w, p0, p1, p2) of a sum of terms (evr_sobo, evr_reward)
+  template <class P>
+  void point_sum(P& p) const {
+    point(p);
+    p.term_w = tc[0].data();
+    p.term_p0 = tc[1].data();
+    p.term_p1 = tc[2].data();
+    p.term_p2 = tc[3].data();
+  }
+};
+
+// qNEI / qLogNEI / qLogEI over one model output (nei_scan.hip)
+struct QneiAcq : ChainAcq<evr_nei, evr_qnei_workspace_doubles, evr_qnei_eval> {
+  int oo = 0, ok = EVR_OBJ_AFFINE;
+  double p0, p1;
+
+  QneiAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
+          const at::Tensor& best_, double obj_a, double obj_b, std::vector<at::Tensor> keep_)
+      : ChainAcq("QneiAcq", "qnei", stm_b, md_b, best_, true, std::move(keep_)), p0(obj_a), p1(obj_b) {
+    TORCH_CHECK(stm.m == 1, "QneiAcq: inconsistent single-output model");
+    improvement(log_, tau_relu, tau_max);
+    g0.m_obj = 1;
+    g0.obj_out = &oo;
+    g0.obj_kind = &ok;
+    g0.obj_p0 = &p0;
+    g0.obj_p1 = &p1;
+  }
+};
+
+// the scalarised, output-constrained qNEI / qLogNEI / qLogEI / qEI over several model outputs
+// (sobo_scan.hip); terms: (out, kind, w, p0, p1, p2)
+struct QsoboAcq : ChainAcq<evr_sobo, evr_qsobo_workspace_doubles, evr_qsobo_eval> {
+  ScanTables tab;
+
+  QsoboAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
+           const at::Tensor& best_, const at::Tensor& terms_, const at::Tensor& cons_, std::vector<at::Tensor> keep_)
+      : ChainAcq("QsoboAcq", "qsobo", stm_b, md_b, best_, true, std::move(keep_)), tab(cls, terms_, cons_, 1) {
+    improvement(log_, tau_relu, tau_max);
+    tab.point_sum(par);
+  }
+};
+
+// qParEGO's qNEI / qLogNEI / qLogEI / qEI: augmented Chebyshev utility, output constraints
+// (parego_scan.hip); terms: (out, kind, p0, p1, A, B)
+struct QparegoAcq : ChainAcq<evr_parego, evr_qparego_workspace_doubles, evr_qparego_eval> {
+  ScanTables tab;
+
+  QparegoAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
+             const at::Tensor& best_, double alpha, const at::Tensor& terms_, const at::Tensor& cons_,
+             std::vector<at::Tensor> keep_)
+      : ChainAcq("QparegoAcq", "qparego", stm_b, md_b, best_, true, std::move(keep_)), tab(cls, terms_, cons_, 2) {
+    improvement(log_, tau_relu, tau_max);
+    par.alpha = alpha;
+    tab.point(par);
+    par.term_p0 = tab.tc[0].data();
+    par.term_p1 = tab.tc[1].data();
+    par.term_a = tab.tc[2].data();
+    par.term_b = tab.tc[3].data();
+  }
+};
+
+// qSR / qUCB / qPI over several model outputs (reward_scan.hip); mode: EVR_REWARD_*; best: one
+// double (read by qPI only); terms / cons as in QsoboAcq
+struct QrewardAcq : ChainAcq<evr_reward, evr_qreward_workspace_doubles, evr_qreward_eval> {
+  ScanTables tab;
+
+  QrewardAcq(const at::Tensor& stm_b, const at::Tensor& md_b, int64_t mode, double ucb_scale, double tau,
+             double infeasible_cost, const at::Tensor& best_, const at::Tensor& terms_, const at::Tensor& cons_,
+             std::vector<at::Tensor> keep_)
+      : ChainAcq("QrewardAcq", "qreward", stm_b, md_b, best_, false, std::move(keep_)), tab(cls, terms_, cons_, 1) {
+    par.mode = (int)mode;
+    par.ucb_scale = ucb_scale;
+    par.tau = tau;
+    par.best = best.data_ptr<double>();
+    par.infeasible_cost = infeasible_cost;
+    tab.point_sum(par);
+  }
+};
+
+template <class A>
+at::Tensor chain_forward(const c10::intrusive_ptr<A>& acq, const at::Tensor& X) {
+  return std::get<0>(acq->eval(X, false));
+}
+
+template <class A>
+std::tuple<at::Tensor, at::Tensor> chain_forward_backward(const c10::intrusive_ptr<A>& acq, const at::Tensor& X) {
   return acq->eval(X, true);
 }
 
-at::Tensor qnei_backward(const NeiPtr& acq, const at::Tensor& X, const at::Tensor& grad_out_) {
+at::Tensor qnei_backward(const c10::intrusive_ptr<QneiAcq>& acq, const at::Tensor& X, const at::Tensor& grad_out_) {
   auto g = dev64(grad_out_, "grad_out");
   auto dX = std::get<1>(acq->eval(X, true));
   TORCH_CHECK(g.numel() == dX.size(0), "qnei_backward: grad_out must have one entry per candidate");
   return dX * g.view({dX.size(0), 1, 1});
 }
 
-// ---------------------------------------------------------------------------------------
-// The acquisition behind torch.ops.everest_amd.qsobo_*: the scalarised, output-constrained
-// qNEI / qLogNEI / qLogEI / qEI over several model outputs through evr_qsobo_eval.  Owns copies
-// of the state / model structs, the term / constraint tables, the incumbent(s) and the base
-// samples per joint batch size, and references to the device tensors they point into.
-// ---------------------------------------------------------------------------------------
-struct QsoboAcq : torch::CustomClassHolder {
-  evr_qnehvi_state stm{};
-  evr_qnehvi_model md{};
-  evr_sobo sb{};
-  std::vector<int> to, tk, co;
-  std::vector<double> tw, tp0, tp1, tp2, cs, ct, ce;
-  at::Tensor best;
-  std::vector<at::Tensor> keep;
-  std::map<int64_t, at::Tensor> zqs;
-  int64_t n_evals = 0;
-
-  // terms: n_term x 6 doubles (out, kind, w, p0, p1, p2); cons: n_con x 4 doubles (out, sign, thr, eta)
-  QsoboAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
-           const at::Tensor& best_, const at::Tensor& terms_, const at::Tensor& cons_, std::vector<at::Tensor> keep_)
-      : keep(std::move(keep_)) {
-    stm = QnehviAcq::from_bytes<evr_qnehvi_state>(stm_b, "model-side state");
-    md = QnehviAcq::from_bytes<evr_qnehvi_model>(md_b, "model");
-    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m >= 1,
-                "QsoboAcq: inconsistent model");
-    best = dev64(best_, "best");
-    TORCH_CHECK(best.numel() == 1 || best.numel() == stm.S, "QsoboAcq: best needs 1 or S values");
-    auto T = terms_.to(at::kCPU, at::kDouble).contiguous();
-    auto C = cons_.to(at::kCPU, at::kDouble).contiguous();
-    TORCH_CHECK(T.dim() == 2 && T.size(1) == 6 && T.size(0) >= 1 && T.size(0) <= EVR_SOBO_MAX_TERMS,
-                "QsoboAcq: terms must be n_term x 6, 1..", EVR_SOBO_MAX_TERMS, " rows");
-    TORCH_CHECK(C.numel() == 0 || (C.dim() == 2 && C.size(1) == 4), "QsoboAcq: constraints must be n_con x 4");
-    const double* t = T.data_ptr<double>();
-    for (int64_t k = 0; k < T.size(0); ++k, t += 6) {
-      to.push_back((int)t[0]);
-      tk.push_back((int)t[1]);
-      tw.push_back(t[2]);
-      tp0.push_back(t[3]);
-      tp1.push_back(t[4]);
-      tp2.push_back(t[5]);
-    }
-    const int64_t nc = C.numel() / 4;
-    const double* c = nc ? C.data_ptr<double>() : nullptr;
-    for (int64_t e = 0; e < nc; ++e, c += 4) {
-      co.push_back((int)c[0]);
-      cs.push_back(c[1]);
-      ct.push_back(c[2]);
-      ce.push_back(c[3]);
-    }
-    sb.log = log_ ? 1 : 0;
-    sb.tau_relu = tau_relu;
-    sb.tau_max = tau_max;
-    sb.best = best.data_ptr<double>();
-    sb.best_stride = best.numel() == 1 ? 0 : 1;
-    sb.n_term = (int)to.size();
-    sb.term_out = to.data();
-    sb.term_kind = tk.data();
-    sb.term_w = tw.data();
-    sb.term_p0 = tp0.data();
-    sb.term_p1 = tp1.data();
-    sb.term_p2 = tp2.data();
-    sb.n_con = (int)nc;
-    sb.con_out = nc ? co.data() : nullptr;
-    sb.con_sign = nc ? cs.data() : nullptr;
-    sb.con_thr = nc ? ct.data() : nullptr;
-    sb.con_eta = nc ? ce.data() : nullptr;
-  }
-
-  void set_samples(int64_t q, const at::Tensor& zq) {
-    TORCH_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "QsoboAcq.set_samples: q = ", q, " outside 1..", EVR_QNG_MAX_Q);
-    auto z = dev64(zq, "zq");
-    TORCH_CHECK(z.numel() == (int64_t)stm.S * q * stm.m, "QsoboAcq.set_samples: zq must be S x q x m");
-    zqs[q] = z;
-  }
-
-  std::tuple<at::Tensor, at::Tensor> eval(const at::Tensor& X_, bool backward) {
-    auto X = dev64(X_, "X");
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-    hipStream_t s = cur_stream();
-    TORCH_CHECK(X.dim() == 3 && X.size(2) == md.d, "qsobo: X must be b x q x d");
-    const int64_t b = X.size(0), q = X.size(1);
-    auto it = zqs.find(q);
-    TORCH_CHECK(it != zqs.end(), "qsobo: no base samples set for q = ", q);
-    evr_qn_general g{};
-    g.q = (int)q;
-    g.zq = it->second.data_ptr<double>();
-    auto acq = at::empty({b}, X.options());
-    at::Tensor dX = backward ? at::empty_like(X) : at::Tensor();
-    if (b == 0) return {acq, dX};
-    auto work = scratch(evr_qsobo_workspace_doubles(&stm, &g, &md, (int)b, backward), X);
-    check(evr_qsobo_eval(s, &stm, &g, &md, &sb, (int)b, X.data_ptr<double>(), nullptr, work.data_ptr<double>(),
-                         acq.data_ptr<double>(), backward ? dX.data_ptr<double>() : nullptr),
-          "qsobo_eval");
-    ++n_evals;
-    return {acq, dX};
-  }
-
-  int64_t evals() const { return n_evals; }
-};
-
-using SoboPtr = c10::intrusive_ptr<QsoboAcq>;
-
-at::Tensor qsobo_forward(const SoboPtr& acq, const at::Tensor& X) { return std::get<0>(acq->eval(X, false)); }
-
-std::tuple<at::Tensor, at::Tensor> qsobo_forward_backward(const SoboPtr& acq, const at::Tensor& X) {
-  return acq->eval(X, true);
-}
-
-// ---------------------------------------------------------------------------------------
-// The acquisition behind torch.ops.everest_amd.qparego_*: qParEGO's qNEI / qLogNEI / qLogEI /
-// qEI over several model outputs (augmented Chebyshev utility, output constraints) through
-// evr_qparego_eval.  Ownership as in QsoboAcq.
-// ---------------------------------------------------------------------------------------
-struct QparegoAcq : torch::CustomClassHolder {
-  evr_qnehvi_state stm{};
-  evr_qnehvi_model md{};
-  evr_parego pg{};
-  std::vector<int> to, tk, co;
-  std::vector<double> tp0, tp1, ta, tb, cs, ct, ce;
-  at::Tensor best;
-  std::vector<at::Tensor> keep;
-  std::map<int64_t, at::Tensor> zqs;
-  int64_t n_evals = 0;
-
-  // terms: n_term x 6 doubles (out, kind, p0, p1, A, B); cons: n_con x 4 doubles (out, sign, thr, eta)
-  QparegoAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
-             const at::Tensor& best_, double alpha, const at::Tensor& terms_, const at::Tensor& cons_,
-             std::vector<at::Tensor> keep_)
-      : keep(std::move(keep_)) {
-    stm = QnehviAcq::from_bytes<evr_qnehvi_state>(stm_b, "model-side state");
-    md = QnehviAcq::from_bytes<evr_qnehvi_model>(md_b, "model");
-    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m >= 1,
-                "QparegoAcq: inconsistent model");
-    best = dev64(best_, "best");
-    TORCH_CHECK(best.numel() == 1 || best.numel() == stm.S, "QparegoAcq: best needs 1 or S values");
-    auto T = terms_.to(at::kCPU, at::kDouble).contiguous();
-    auto C = cons_.to(at::kCPU, at::kDouble).contiguous();
-    TORCH_CHECK(T.dim() == 2 && T.size(1) == 6 && T.size(0) >= 2 && T.size(0) <= EVR_SOBO_MAX_TERMS,
-                "QparegoAcq: terms must be n_term x 6, 2..", EVR_SOBO_MAX_TERMS, " rows");
-    TORCH_CHECK(C.numel() == 0 || (C.dim() == 2 && C.size(1) == 4), "QparegoAcq: constraints must be n_con x 4");
-    const double* t = T.data_ptr<double>();
-    for (int64_t k = 0; k < T.size(0); ++k, t += 6) {
-      to.push_back((int)t[0]);
-      tk.push_back((int)t[1]);
-      tp0.push_back(t[2]);
-      tp1.push_back(t[3]);
-      ta.push_back(t[4]);
-      tb.push_back(t[5]);
-    }
-    const int64_t nc = C.numel() / 4;
-    const double* c = nc ? C.data_ptr<double>() : nullptr;
-    for (int64_t e = 0; e < nc; ++e, c += 4) {
-      co.push_back((int)c[0]);
-      cs.push_back(c[1]);
-      ct.push_back(c[2]);
-      ce.push_back(c[3]);
-    }
-    pg.log = log_ ? 1 : 0;
-    pg.tau_relu = tau_relu;
-    pg.tau_max = tau_max;
-    pg.best = best.data_ptr<double>();
-    pg.best_stride = best.numel() == 1 ? 0 : 1;
-    pg.alpha = alpha;
-    pg.n_term = (int)to.size();
-    pg.term_out = to.data();
-    pg.term_kind = tk.data();
-    pg.term_p0 = tp0.data();
-    pg.term_p1 = tp1.data();
-    pg.term_a = ta.data();
-    pg.term_b = tb.data();
-    pg.n_con = (int)nc;
-    pg.con_out = nc ? co.data() : nullptr;
-    pg.con_sign = nc ? cs.data() : nullptr;
-    pg.con_thr = nc ? ct.data() : nullptr;
-    pg.con_eta = nc ? ce.data() : nullptr;
-  }
-
-  void set_samples(int64_t q, const at::Tensor& zq) {
-    TORCH_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "QparegoAcq.set_samples: q = ", q, " outside 1..", EVR_QNG_MAX_Q);
-    auto z = dev64(zq, "zq");
-    TORCH_CHECK(z.numel() == (int64_t)stm.S * q * stm.m, "QparegoAcq.set_samples: zq must be S x q x m");
-    zqs[q] = z;
-  }
-
-  std::tuple<at::Tensor, at::Tensor> eval(const at::Tensor& X_, bool backward) {
-    auto X = dev64(X_, "X");
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-    hipStream_t s = cur_stream();
-    TORCH_CHECK(X.dim() == 3 && X.size(2) == md.d, "qparego: X must be b x q x d");
-    const int64_t b = X.size(0), q = X.size(1);
-    auto it = zqs.find(q);
-    TORCH_CHECK(it != zqs.end(), "qparego: no base samples set for q = ", q);
-    evr_qn_general g{};
-    g.q = (int)q;
-    g.zq = it->second.data_ptr<double>();
-    auto acq = at::empty({b}, X.options());
-    at::Tensor dX = backward ? at::empty_like(X) : at::Tensor();
-    if (b == 0) return {acq, dX};
-    auto work = scratch(evr_qparego_workspace_doubles(&stm, &g, &md, (int)b, backward), X);
-    check(evr_qparego_eval(s, &stm, &g, &md, &pg, (int)b, X.data_ptr<double>(), nullptr, work.data_ptr<double>(),
-                           acq.data_ptr<double>(), backward ? dX.data_ptr<double>() : nullptr),
-          "qparego_eval");
-    ++n_evals;
-    return {acq, dX};
-  }
-
-  int64_t evals() const { return n_evals; }
-};
-
-using ParegoPtr = c10::intrusive_ptr<QparegoAcq>;
-
-at::Tensor qparego_forward(const ParegoPtr& acq, const at::Tensor& X) { return std::get<0>(acq->eval(X, false)); }
-
-std::tuple<at::Tensor, at::Tensor> qparego_forward_backward(const ParegoPtr& acq, const at::Tensor& X) {
-  return acq->eval(X, true);
-}
-
-// ---------------------------------------------------------------------------------------
-// The acquisition behind torch.ops.everest_amd.qreward_*: qSR / qUCB / qPI over several model
-// outputs (reward scans of reward_scan.hip) through evr_qreward_eval.  Ownership as in QsoboAcq.
-// ---------------------------------------------------------------------------------------
-struct QrewardAcq : torch::CustomClassHolder {
-  evr_qnehvi_state stm{};
-  evr_qnehvi_model md{};
-  evr_reward rw{};
-  std::vector<int> to, tk, co;
-  std::vector<double> tw, tp0, tp1, tp2, cs, ct, ce;
-  at::Tensor best;
-  std::vector<at::Tensor> keep;
-  std::map<int64_t, at::Tensor> zqs;
-  int64_t n_evals = 0;
-
-  // mode: EVR_REWARD_*; best: one double (read by qPI only); terms / cons as in QsoboAcq
-  QrewardAcq(const at::Tensor& stm_b, const at::Tensor& md_b, int64_t mode, double ucb_scale, double tau,
-             double infeasible_cost, const at::Tensor& best_, const at::Tensor& terms_, const at::Tensor& cons_,
-             std::vector<at::Tensor> keep_)
-      : keep(std::move(keep_)) {
-    stm = QnehviAcq::from_bytes<evr_qnehvi_state>(stm_b, "model-side state");
-    md = QnehviAcq::from_bytes<evr_qnehvi_model>(md_b, "model");
-    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m >= 1,
-                "QrewardAcq: inconsistent model");
-    best = dev64(best_, "best");
-    TORCH_CHECK(best.numel() == 1, "QrewardAcq: best needs one value");
-    auto T = terms_.to(at::kCPU, at::kDouble).contiguous();
-    auto C = cons_.to(at::kCPU, at::kDouble).contiguous();
-    TORCH_CHECK(T.dim() == 2 && T.size(1) == 6 && T.size(0) >= 1 && T.size(0) <= EVR_SOBO_MAX_TERMS,
-                "QrewardAcq: terms must be n_term x 6, 1..", EVR_SOBO_MAX_TERMS, " rows");
-    TORCH_CHECK(C.numel() == 0 || (C.dim() == 2 && C.size(1) == 4), "QrewardAcq: constraints must be n_con x 4");
-    const double* t = T.data_ptr<double>();
-    for (int64_t k = 0; k < T.size(0); ++k, t += 6) {
-      to.push_back((int)t[0]);
-      tk.push_back((int)t[1]);
-      tw.push_back(t[2]);
-      tp0.push_back(t[3]);
-      tp1.push_back(t[4]);
-      tp2.push_back(t[5]);
-    }
-    const int64_t nc = C.numel() / 4;
-    const double* c = nc ? C.data_ptr<double>() : nullptr;
-    for (int64_t e = 0; e < nc; ++e, c += 4) {
-      co.push_back((int)c[0]);
-      cs.push_back(c[1]);
-      ct.push_back(c[2]);
-      ce.push_back(c[3]);
-    }
-    rw.mode = (int)mode;
-    rw.ucb_scale = ucb_scale;
-    rw.tau = tau;
-    rw.best = best.data_ptr<double>();
-    rw.infeasible_cost = infeasible_cost;
-    rw.n_term = (int)to.size();
-    rw.term_out = to.data();
-    rw.term_kind = tk.data();
-    rw.term_w = tw.data();
-    rw.term_p0 = tp0.data();
-    rw.term_p1 = tp1.data();
-    rw.term_p2 = tp2.data();
-    rw.n_con = (int)nc;
-    rw.con_out = nc ? co.data() : nullptr;
-    rw.con_sign = nc ? cs.data() : nullptr;
-    rw.con_thr = nc ? ct.data() : nullptr;
-    rw.con_eta = nc ? ce.data() : nullptr;
-  }
-
-  void set_samples(int64_t q, const at::Tensor& zq) {
-    TORCH_CHECK(q >= 1 && q <= EVR_QNG_MAX_Q, "QrewardAcq.set_samples: q = ", q, " outside 1..", EVR_QNG_MAX_Q);
-    auto z = dev64(zq, "zq");
-    TORCH_CHECK(z.numel() == (int64_t)stm.S * q * stm.m, "QrewardAcq.set_samples: zq must be S x q x m");
-    zqs[q] = z;
-  }
-
-  std::tuple<at::Tensor, at::Tensor> eval(const at::Tensor& X_, bool backward) {
-    auto X = dev64(X_, "X");
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-    hipStream_t s = cur_stream();
-    TORCH_CHECK(X.dim() == 3 && X.size(2) == md.d, "qreward: X must be b x q x d");
-    const int64_t b = X.size(0), q = X.size(1);
-    auto it = zqs.find(q);
-    TORCH_CHECK(it != zqs.end(), "qreward: no base samples set for q = ", q);
-    evr_qn_general g{};
-    g.q = (int)q;
-    g.zq = it->second.data_ptr<double>();
-    auto acq = at::empty({b}, X.options());
-    at::Tensor dX = backward ? at::empty_like(X) : at::Tensor();
-    if (b == 0) return {acq, dX};
-    auto work = scratch(evr_qreward_workspace_doubles(&stm, &g, &md, (int)b, backward), X);
-    check(evr_qreward_eval(s, &stm, &g, &md, &rw, (int)b, X.data_ptr<double>(), nullptr, work.data_ptr<double>(),
-                           acq.data_ptr<double>(), backward ? dX.data_ptr<double>() : nullptr),
-          "qreward_eval");
-    ++n_evals;
-    return {acq, dX};
-  }
-
-  int64_t evals() const { return n_evals; }
-};
-
-using RewardPtr = c10::intrusive_ptr<QrewardAcq>;
-
-at::Tensor qreward_forward(const RewardPtr& acq, const at::Tensor& X) { return std::get<0>(acq->eval(X, false)); }
-
-std::tuple<at::Tensor, at::Tensor> qreward_forward_backward(const RewardPtr& acq, const at::Tensor& X) {
-  return acq->eval(X, true);
+// a ChainAcq class: its constructor, set_samples and evals
+template <class A, class... Init>
+void def_chain(torch::Library& m, const char* name) {
+  m.class_<A>(name)
+      .def(torch::init<Init...>())
+      .def("set_samples", [](const c10::intrusive_ptr<A>& a, int64_t q, const at::Tensor& zq) { a->set_samples(q, zq); })
+      .def("evals", [](const c10::intrusive_ptr<A>& a) { return a->n_evals; });
 }
 
 }  // namespace
 
 TORCH_LIBRARY(everest_amd, m) {
-  m.class_<QrewardAcq>("QrewardAcq")
-      .def(torch::init<at::Tensor, at::Tensor, int64_t, double, double, double, at::Tensor, at::Tensor, at::Tensor,
-                       std::vector<at::Tensor>>())
-      .def("set_samples", &QrewardAcq::set_samples)
-      .def("evals", &QrewardAcq::evals);
-  m.class_<QparegoAcq>("QparegoAcq")
-      .def(torch::init<at::Tensor, at::Tensor, bool, double, double, at::Tensor, double, at::Tensor, at::Tensor,
-                       std::vector<at::Tensor>>())
-      .def("set_samples", &QparegoAcq::set_samples)
-      .def("evals", &QparegoAcq::evals);
-  m.class_<QsoboAcq>("QsoboAcq")
-      .def(torch::init<at::Tensor, at::Tensor, bool, double, double, at::Tensor, at::Tensor, at::Tensor,
-                       std::vector<at::Tensor>>())
-      .def("set_samples", &QsoboAcq::set_samples)
-      .def("evals", &QsoboAcq::evals);
-  m.class_<QneiAcq>("QneiAcq")
-      .def(torch::init<at::Tensor, at::Tensor, bool, double, double, at::Tensor, double, double,
-                       std::vector<at::Tensor>>())
-      .def("set_samples", &QneiAcq::set_samples)
-      .def("evals", &QneiAcq::evals);
+  using T = at::Tensor;
+  using Keep = std::vector<at::Tensor>;
+  def_chain<QrewardAcq, T, T, int64_t, double, double, double, T, T, T, Keep>(m, "QrewardAcq");
+  def_chain<QparegoAcq, T, T, bool, double, double, T, double, T, T, Keep>(m, "QparegoAcq");
+  def_chain<QsoboAcq, T, T, bool, double, double, T, T, T, Keep>(m, "QsoboAcq");
+  def_chain<QneiAcq, T, T, bool, double, double, T, double, double, Keep>(m, "QneiAcq");
   m.class_<QnehviAcq>("QnehviAcq")
       .def(torch::init<at::Tensor, at::Tensor, at::Tensor, bool, bool, std::vector<at::Tensor>>())
       .def("set_general", &QnehviAcq::set_general)
@@ -749,13 +558,13 @@ TORCH_LIBRARY_IMPL(everest_amd, CUDA, m) {
   m.impl("qnehvi_forward", &qnehvi_forward);
   m.impl("qnehvi_forward_backward", &qnehvi_forward_backward);
   m.impl("qnehvi_backward", &qnehvi_backward);
-  m.impl("qnei_forward", &qnei_forward);
-  m.impl("qnei_forward_backward", &qnei_forward_backward);
+  m.impl("qnei_forward", &chain_forward<QneiAcq>);
+  m.impl("qnei_forward_backward", &chain_forward_backward<QneiAcq>);
   m.impl("qnei_backward", &qnei_backward);
-  m.impl("qsobo_forward", &qsobo_forward);
-  m.impl("qsobo_forward_backward", &qsobo_forward_backward);
-  m.impl("qparego_forward", &qparego_forward);
-  m.impl("qparego_forward_backward", &qparego_forward_backward);
-  m.impl("qreward_forward", &qreward_forward);
-  m.impl("qreward_forward_backward", &qreward_forward_backward);
+  m.impl("qsobo_forward", &chain_forward<QsoboAcq>);
+  m.impl("qsobo_forward_backward", &chain_forward_backward<QsoboAcq>);
+  m.impl("qparego_forward", &chain_forward<QparegoAcq>);
+  m.impl("qparego_forward_backward", &chain_forward_backward<QparegoAcq>);
+  m.impl("qreward_forward", &chain_forward<QrewardAcq>);
+  m.impl("qreward_forward_backward", &chain_forward_backward<QrewardAcq>);
 }

@@ -523,13 +523,18 @@ def model_state(n, nb, S, c, ym, ys, kxx, no_h: bool = False, m: int = 1) -> Evr
     return st
 
 
+def _improvement(st, log: bool, tau_relu: float, tau_max: float, best: torch.Tensor):
+    """The head the improvement scans' structs share: log mode, temperatures and ``best`` (device;
+    S per-sample incumbents, or one value: stride 0).  Returns st."""
+    best = _dev(best, "best")
+    st.log, st.tau_relu, st.tau_max = int(bool(log)), float(tau_relu), float(tau_max)
+    st.best, st.best_stride = best.data_ptr(), 0 if best.numel() == 1 else 1
+    return st
+
+
 def nei_struct(log: bool, tau_relu: float, tau_max: float, best: torch.Tensor) -> "_native.EvrNei":
     """evr_nei over ``best`` (device; S per-sample incumbents, or one value: stride 0)."""
-    best = _dev(best, "best")
-    nei = _native.EvrNei()
-    nei.log, nei.tau_relu, nei.tau_max = int(bool(log)), float(tau_relu), float(tau_max)
-    nei.best, nei.best_stride = best.data_ptr(), 0 if best.numel() == 1 else 1
-    return nei
+    return _improvement(_native.EvrNei(), log, tau_relu, tau_max, best)
 
 
 def nei_scan(Y: torch.Tensor, q: int, best: torch.Tensor, obj_a: float, obj_b: float, log: bool = False,
@@ -561,23 +566,27 @@ def qnei_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviMod
               X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
     """qNEI / qLogNEI / qLogEI (evr_qnei_eval): X (b*q) x d raw candidates -> acq (b)
     [, dX (b*q) x d]."""
-    X = _dev(X, "X")
-    q = int(g.q)
-    bq, d = X.shape
-    if bq % q:
-        raise ValueError(f"{bq} rows are not a multiple of q = {q}")
-    b = bq // q
-    lib = _native.load()
-    work = _workspace(lib.evr_qnei_workspace_doubles(ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), b,
-                                                     int(backward)), X.device)
-    acq = torch.empty(b, dtype=torch.float64, device=X.device)
-    dX = torch.empty_like(X) if backward else None
-    call("evr_qnei_eval", _stream(), ctypes.byref(stm), ctypes.byref(g), ctypes.byref(model), ctypes.byref(nei), b,
-         X.data_ptr(), _p(None if gout is None else _dev(gout, "gout")), work.data_ptr(), acq.data_ptr(), _p(dX))
-    return acq, dX
+    return _utility_eval("evr_qnei", stm, g, model, nei, X, backward, gout)
 
 
 OBJ_SIGMOID, OBJ_TARGET = 2, 3
+
+
+def _table_arrays(terms, constraints):
+    """Host arrays of a spec's term rows (out, kind, four doubles) and constraint rows (out, sign,
+    thr, eta), column by column; without constraints one placeholder row keeps the pointers valid."""
+    tarrs = (np.array([t[0] for t in terms], np.int32), np.array([t[1] for t in terms], np.int32)) + tuple(
+        np.array([t[i] for t in terms], np.float64) for i in (2, 3, 4, 5))
+    cs = constraints or [(0, 0.0, 0.0, 1.0)]
+    carrs = (np.array([c[0] for c in cs], np.int32), np.array([c[1] for c in cs], np.float64),
+             np.array([c[2] for c in cs], np.float64), np.array([c[3] for c in cs], np.float64))
+    return tarrs, carrs
+
+
+def _point_tables(st, spec):
+    """The fields every scan struct names alike: the table sizes and the constraint columns."""
+    st.n_term, st.n_con = len(spec.terms), len(spec.constraints)
+    st.con_out, st.con_sign, st.con_thr, st.con_eta = (a.ctypes.data for a in spec._carrs)
 
 
 class SoboSpec:
@@ -602,24 +611,15 @@ class SoboSpec:
         for _, k, *_ in self.terms:
             if k not in (OBJ_AFFINE, OBJ_CLOSE_TO_TARGET, OBJ_SIGMOID, OBJ_TARGET):
                 raise ValueError(f"sobo scan: term kind {k}")
-        tm = self.terms
-        self._tarrs = (np.array([t[0] for t in tm], np.int32), np.array([t[1] for t in tm], np.int32)) + tuple(
-            np.array([t[i] for t in tm], np.float64) for i in (2, 3, 4, 5))
-        cs = self.constraints or [(0, 0.0, 0.0, 1.0)]
-        self._carrs = (np.array([c[0] for c in cs], np.int32), np.array([c[1] for c in cs], np.float64),
-                       np.array([c[2] for c in cs], np.float64), np.array([c[3] for c in cs], np.float64))
+        self._tarrs, self._carrs = _table_arrays(self.terms, self.constraints)
 
     def struct(self, log: bool, tau_relu: float, tau_max: float, best: torch.Tensor) -> "_native.EvrSobo":
         """evr_sobo over ``best`` (device; S per-sample incumbents, or one value: stride 0).  The
         struct points into this spec's host arrays and into ``best``: keep both alive."""
-        best = _dev(best, "best")
-        sb = _native.EvrSobo()
-        sb.log, sb.tau_relu, sb.tau_max = int(bool(log)), float(tau_relu), float(tau_max)
-        sb.best, sb.best_stride = best.data_ptr(), 0 if best.numel() == 1 else 1
-        sb.n_term, sb.n_con = len(self.terms), len(self.constraints)
+        sb = _improvement(_native.EvrSobo(), log, tau_relu, tau_max, best)
+        _point_tables(sb, self)
         (sb.term_out, sb.term_kind, sb.term_w, sb.term_p0, sb.term_p1,
          sb.term_p2) = (a.ctypes.data for a in self._tarrs)
-        sb.con_out, sb.con_sign, sb.con_thr, sb.con_eta = (a.ctypes.data for a in self._carrs)
         return sb
 
     @staticmethod
@@ -658,21 +658,31 @@ def sobo_scan(Y: torch.Tensor, q: int, best: torch.Tensor, spec: SoboSpec, log: 
     return _utility_scan("evr_sobo_scan", Y, q, best, spec, log, tau_relu, tau_max, flags, gout, backward)
 
 
-def _utility_scan(symbol: str, Y, q, best, spec, log, tau_relu, tau_max, flags, gout, backward):
-    Y, best = _dev(Y, "Y"), _dev(best, "best")
+def _scan_args(Y, q, spec, flags, gout):
+    """The checks the scans over several model outputs share: Y (S x m_model x (b*q)) against the
+    spec and q, flags (m_model x b) and gout (b).  Returns (Y, q, b, flags, gout) as the call
+    takes them."""
+    Y = _dev(Y, "Y")
     S, m, bq = Y.shape
     q = int(q)
     if m != spec.m_model:
         raise ValueError(f"Y has {m} outputs, the spec {spec.m_model}")
     if q < 1 or bq % q:
         raise ValueError(f"{bq} columns are not a multiple of q = {q}")
-    if best.numel() not in (1, S):
-        raise ValueError(f"best needs 1 or S = {S} values, got {best.numel()}")
     b = bq // q
     flags = None if flags is None else _dev(flags, "flags", torch.int32)
     gout = None if gout is None else _dev(gout, "gout")
     if (flags is not None and flags.numel() != m * b) or (gout is not None and gout.numel() != b):
         raise ValueError("flags need one entry per (output, candidate), gout one per candidate")
+    return Y, q, b, flags, gout
+
+
+def _utility_scan(symbol: str, Y, q, best, spec, log, tau_relu, tau_max, flags, gout, backward):
+    Y, q, b, flags, gout = _scan_args(Y, q, spec, flags, gout)
+    S, m, _ = Y.shape
+    best = _dev(best, "best")
+    if best.numel() not in (1, S):
+        raise ValueError(f"best needs 1 or S = {S} values, got {best.numel()}")
     acq = torch.empty(b, dtype=torch.float64, device=Y.device)
     dY = torch.empty_like(Y) if backward else None
     sb = spec.struct(log, tau_relu, tau_max, best)
@@ -731,25 +741,16 @@ class ParegoSpec:
                 raise ValueError(f"parego scan: term kind {k}")
             if not A > 0.0:
                 raise ValueError(f"parego scan: term scale A = {A} must be positive")
-        tm = self.terms
-        self._tarrs = (np.array([t[0] for t in tm], np.int32), np.array([t[1] for t in tm], np.int32)) + tuple(
-            np.array([t[i] for t in tm], np.float64) for i in (2, 3, 4, 5))
-        cs = self.constraints or [(0, 0.0, 0.0, 1.0)]
-        self._carrs = (np.array([c[0] for c in cs], np.int32), np.array([c[1] for c in cs], np.float64),
-                       np.array([c[2] for c in cs], np.float64), np.array([c[3] for c in cs], np.float64))
+        self._tarrs, self._carrs = _table_arrays(self.terms, self.constraints)
 
     def struct(self, log: bool, tau_relu: float, tau_max: float, best: torch.Tensor) -> "_native.EvrParego":
         """evr_parego over ``best`` (device; S per-sample incumbents, or one value: stride 0).  The
         struct points into this spec's host arrays and into ``best``: keep both alive."""
-        best = _dev(best, "best")
-        pg = _native.EvrParego()
-        pg.log, pg.tau_relu, pg.tau_max = int(bool(log)), float(tau_relu), float(tau_max)
-        pg.best, pg.best_stride = best.data_ptr(), 0 if best.numel() == 1 else 1
+        pg = _improvement(_native.EvrParego(), log, tau_relu, tau_max, best)
         pg.alpha = self.alpha
-        pg.n_term, pg.n_con = len(self.terms), len(self.constraints)
+        _point_tables(pg, self)
         (pg.term_out, pg.term_kind, pg.term_p0, pg.term_p1, pg.term_a,
          pg.term_b) = (a.ctypes.data for a in self._tarrs)
-        pg.con_out, pg.con_sign, pg.con_thr, pg.con_eta = (a.ctypes.data for a in self._carrs)
         return pg
 
     def term_values(self, Y):
@@ -824,10 +825,9 @@ def reward_struct(spec: SoboSpec, mode: int, beta: float = 0.2, tau: float = 1e-
         if not float(infeasible_cost) >= 0.0:
             raise ValueError(f"reward scan: infeasible cost {infeasible_cost} must be non-negative")
     rw.infeasible_cost = float(infeasible_cost)
-    rw.n_term, rw.n_con = len(spec.terms), len(spec.constraints)
+    _point_tables(rw, spec)
     (rw.term_out, rw.term_kind, rw.term_w, rw.term_p0, rw.term_p1,
      rw.term_p2) = (a.ctypes.data for a in spec._tarrs)
-    rw.con_out, rw.con_sign, rw.con_thr, rw.con_eta = (a.ctypes.data for a in spec._carrs)
     return rw
 
 
@@ -836,19 +836,9 @@ def reward_scan(Y: torch.Tensor, q: int, spec: SoboSpec, mode: int, beta: float 
                 flags: Optional[torch.Tensor] = None, gout: Optional[torch.Tensor] = None, backward: bool = False):
     """qSR / qUCB / qPI scan alone (evr_reward_scan): Y S x m_model x (b*q) joint samples (point i
     of candidate c at column c*q + i) -> (acq (b), dY like Y | None).  flags: m_model x b."""
-    Y = _dev(Y, "Y")
-    S, m, bq = Y.shape
-    q = int(q)
-    if m != spec.m_model:
-        raise ValueError(f"Y has {m} outputs, the spec {spec.m_model}")
-    if q < 1 or bq % q:
-        raise ValueError(f"{bq} columns are not a multiple of q = {q}")
-    b = bq // q
+    Y, q, b, flags, gout = _scan_args(Y, q, spec, flags, gout)
+    S, m, _ = Y.shape
     best = None if best is None else _dev(best, "best")
-    flags = None if flags is None else _dev(flags, "flags", torch.int32)
-    gout = None if gout is None else _dev(gout, "gout")
-    if (flags is not None and flags.numel() != m * b) or (gout is not None and gout.numel() != b):
-        raise ValueError("flags need one entry per (output, candidate), gout one per candidate")
     acq = torch.empty(b, dtype=torch.float64, device=Y.device)
     dY = torch.empty_like(Y) if backward else None
     rw = reward_struct(spec, mode, beta, tau, best, infeasible_cost)

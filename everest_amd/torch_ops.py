@@ -21,6 +21,10 @@ AcquisitionFunction.forward protocols called at bofire/strategies/predictives/bo
                                          constraints, keep)
     torch.ops.everest_amd.qreward_forward / qreward_forward_backward   (qSR, qUCB, qPI)
 
+The five autograd wrappers (QnehviFunction, QneiFunction, QsoboFunction, QparegoFunction,
+QrewardFunction) are instances of one body, _chain_function(prefix), that differ in the operator
+prefix only.
+
 No fallback: a missing library raises NativeLibraryError."""
 from __future__ import annotations
 
@@ -49,106 +53,34 @@ def load():
     return torch.ops.everest_amd
 
 
-class QnehviFunction(torch.autograd.Function):
-    """acq = qNEHVI / qEHVI(X) through the torch operators on a
-    torch.classes.everest_amd.QnehviAcq (which owns the acquisition state and caches its
-    plans).  When X needs a gradient the forward runs qnehvi_forward_backward — ONE device
-    chain for the value and the analytic gradient — and saves dX; backward only scales it by
-    grad_out (candidates are independent)."""
+def _chain_function(prefix: str, doc: str):
+    """The autograd.Function over torch.ops.everest_amd.<prefix>_forward / _forward_backward on the
+    matching torch.classes.everest_amd object.  When X needs a gradient the forward runs
+    <prefix>_forward_backward — ONE device chain for the value and the analytic gradient — and
+    saves dX; backward only scales it by grad_out (candidates are independent; dX is b x d on the
+    qNEHVI q = 1 fast path, b x q x d otherwise)."""
 
-    @staticmethod
     def forward(ctx, X: torch.Tensor, acq):
         ops = load()
         if ctx.needs_input_grad[0]:
-            a, dX = ops.qnehvi_forward_backward(acq, X)
+            a, dX = getattr(ops, prefix + "_forward_backward")(acq, X)
             ctx.save_for_backward(dX)
             return a
         ctx.save_for_backward(None)
-        return ops.qnehvi_forward(acq, X)
+        return getattr(ops, prefix + "_forward")(acq, X)
 
-    @staticmethod
     def backward(ctx, grad_out: torch.Tensor):
         (dX,) = ctx.saved_tensors
-        shape = (dX.shape[0],) + (1,) * (dX.dim() - 1)
-        return dX * grad_out.reshape(shape), None
+        return dX * grad_out.reshape((dX.shape[0],) + (1,) * (dX.dim() - 1)), None
+
+    return type(f"Q{prefix[1:]}Function", (torch.autograd.Function,),
+                {"__doc__": doc, "forward": staticmethod(forward), "backward": staticmethod(backward)})
 
 
-class QneiFunction(torch.autograd.Function):
-    """acq = qNEI / qLogNEI / qLogEI(X), X b x q x d, through torch.ops.everest_amd.qnei_* on a
-    torch.classes.everest_amd.QneiAcq; as QnehviFunction, one device chain gives the value and
-    the analytic gradient, and backward scales the saved dX by grad_out."""
-
-    @staticmethod
-    def forward(ctx, X: torch.Tensor, acq):
-        ops = load()
-        if ctx.needs_input_grad[0]:
-            a, dX = ops.qnei_forward_backward(acq, X)
-            ctx.save_for_backward(dX)
-            return a
-        ctx.save_for_backward(None)
-        return ops.qnei_forward(acq, X)
-
-    @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        (dX,) = ctx.saved_tensors
-        return dX * grad_out.reshape(-1, 1, 1), None
-
-
-class QsoboFunction(torch.autograd.Function):
-    """acq = QSoboNEI / QSoboLogNEI / QSoboLogEI(X), X b x q x d, through
-    torch.ops.everest_amd.qsobo_* on a torch.classes.everest_amd.QsoboAcq; as QneiFunction."""
-
-    @staticmethod
-    def forward(ctx, X: torch.Tensor, acq):
-        ops = load()
-        if ctx.needs_input_grad[0]:
-            a, dX = ops.qsobo_forward_backward(acq, X)
-            ctx.save_for_backward(dX)
-            return a
-        ctx.save_for_backward(None)
-        return ops.qsobo_forward(acq, X)
-
-    @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        (dX,) = ctx.saved_tensors
-        return dX * grad_out.reshape(-1, 1, 1), None
-
-
-class QparegoFunction(torch.autograd.Function):
-    """acq = QParegoNEI / QParegoLogNEI / QParegoLogEI(X), X b x q x d, through
-    torch.ops.everest_amd.qparego_* on a torch.classes.everest_amd.QparegoAcq; as QneiFunction."""
-
-    @staticmethod
-    def forward(ctx, X: torch.Tensor, acq):
-        ops = load()
-        if ctx.needs_input_grad[0]:
-            a, dX = ops.qparego_forward_backward(acq, X)
-            ctx.save_for_backward(dX)
-            return a
-        ctx.save_for_backward(None)
-        return ops.qparego_forward(acq, X)
-
-    @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        (dX,) = ctx.saved_tensors
-        return dX * grad_out.reshape(-1, 1, 1), None
-
-
-class QrewardFunction(torch.autograd.Function):
-    """acq = QSoboSR / QSoboUCB / QSoboPI(X), X b x q x d, through torch.ops.everest_amd.qreward_*
-    on a torch.classes.everest_amd.QrewardAcq; as QneiFunction."""
-
-    @staticmethod
-    def forward(ctx, X: torch.Tensor, acq):
-        ops = load()
-        if ctx.needs_input_grad[0]:
-            a, dX = ops.qreward_forward_backward(acq, X)
-            ctx.save_for_backward(dX)
-            return a
-        ctx.save_for_backward(None)
-        return ops.qreward_forward(acq, X)
-
-    @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        (dX,) = ctx.saved_tensors
-        return dX * grad_out.reshape(-1, 1, 1), None
+QnehviFunction = _chain_function("qnehvi", "acq = qNEHVI / qEHVI(X) on a QnehviAcq (which owns the acquisition "
+                                           "state and caches its plans); X b x d (q = 1 fast path) or b x q x d.")
+QneiFunction = _chain_function("qnei", "acq = qNEI / qLogNEI / qLogEI(X), X b x q x d, on a QneiAcq.")
+QsoboFunction = _chain_function("qsobo", "acq = QSoboNEI / QSoboLogNEI / QSoboLogEI(X), X b x q x d, on a QsoboAcq.")
+QparegoFunction = _chain_function("qparego",
+                                  "acq = QParegoNEI / QParegoLogNEI / QParegoLogEI(X), X b x q x d, on a QparegoAcq.")
+QrewardFunction = _chain_function("qreward", "acq = QSoboSR / QSoboUCB / QSoboPI(X), X b x q x d, on a QrewardAcq.")

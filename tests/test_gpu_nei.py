@@ -203,6 +203,22 @@ def test_autograd_equals_forward_backward(state):
     assert g.shape == flat.shape and torch.equal(acqf(flat), a)
 
 
+def test_qnei_operators_equal_forward_backward(state):
+    """torch.ops.everest_amd.qnei_forward / qnei_forward_backward / qnei_backward called directly
+    on the QneiAcq give forward_backward's values bit for bit (qnei_backward: dX scaled by w)."""
+    rng = np.random.default_rng(6)
+    for name in ("QNEI", "QLogNEI"):
+        acqf, _ = _build(state, name, 0, True, rng)
+        Xc = torch.tensor(rng.uniform(size=(5, 2, 4)), device="cuda")
+        acq, dX = acqf.forward_backward(Xc)
+        tacq = acqf._torch_acq(2)
+        assert torch.equal(torch.ops.everest_amd.qnei_forward(tacq, Xc), acq), name
+        a2, d2 = torch.ops.everest_amd.qnei_forward_backward(tacq, Xc)
+        assert torch.equal(a2, acq) and torch.equal(d2, dX), name
+        w = torch.tensor(rng.uniform(0.5, 2.0, size=5), device="cuda")
+        assert torch.equal(torch.ops.everest_amd.qnei_backward(tacq, Xc, w), dX * w.view(-1, 1, 1)), name
+
+
 # ---------------------------------------------------------------------------------------
 # SoboStrategy
 # ---------------------------------------------------------------------------------------
