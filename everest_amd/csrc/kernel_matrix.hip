@@ -18,7 +18,14 @@ namespace evr {
 constexpr int KT = 64;
 constexpr int KMAXD = 64;
 
-template <int RA, int KIND>
+// Member form of the train-matrix kernels (evr_kernel_matrix_members): the kernels take one
+// trailing argument more, nvalid — member b reads its own rows X + b n d, and an entry whose
+// row or column is >= nvalid[b] is the identity's.  The shared-X instantiations have an empty
+// pack: their arguments and their code are what they were.
+__device__ __forceinline__ const int* member_nvalid() { return nullptr; }
+__device__ __forceinline__ const int* member_nvalid(const int* nvalid) { return nvalid; }
+
+template <int RA, int KIND, class... NV>
 __global__ __launch_bounds__(256) void kmat_kernel(int kind, int n1, int n2, int d, const double* __restrict__ X1,
                                                    const double* __restrict__ sh1, const double* __restrict__ sc1,
                                                    const double* __restrict__ X2, const double* __restrict__ sh2,
@@ -26,7 +33,9 @@ __global__ __launch_bounds__(256) void kmat_kernel(int kind, int n1, int n2, int
                                                    const double* __restrict__ os, const double* __restrict__ dg,
                                                    double* __restrict__ K,
                                                    const unsigned long long* seq_src, unsigned long long* seq_dst,
-                                                   double* __restrict__ x_dst, int* __restrict__ zero_dst, int nzero) {
+                                                   double* __restrict__ x_dst, int* __restrict__ zero_dst, int nzero,
+                                                   NV... nv) {
+  constexpr bool MEMBERS = sizeof...(NV) > 0;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   // the posterior's arrival counters (post_proj_kernel) zeroed by the first workgroup: the
   // projection launches after this kernel has completed
@@ -44,6 +53,10 @@ __global__ __launch_bounds__(256) void kmat_kernel(int kind, int n1, int n2, int
   double* Bt = smem + 16 * RA * ld;  // KT x ld
   const double* lsb = ls + (size_t)b * d;
   const int tid = threadIdx.x;
+  if constexpr (MEMBERS) {   // n1 == n2, X1 == X2: the members' inputs
+    X1 += (size_t)b * n1 * d;
+    X2 = X1;
+  }
   // d < 16: at most 4 staging elements per thread; all loads issued before the first wait
   double xv[4], xw[4];
 #pragma unroll
@@ -123,6 +136,10 @@ __global__ __launch_bounds__(256) void kmat_kernel(int kind, int n1, int n2, int
       if (j < n2) {
         double v = scale * kernel_value_t(KIND, acc[a][c], kexp);
         if (i == j) v += dadd;
+        if constexpr (MEMBERS) {
+          const int nvb = member_nvalid(nv...)[b];
+          if (i >= nvb || j >= nvb) v = i == j ? 1.0 : 0.0;
+        }
         Kb[(size_t)i * n2 + j] = v;
       }
     }
@@ -353,11 +370,13 @@ __global__ __launch_bounds__(256) void kmat_mfma_kernel(int kind, int n1, int n2
 // tile in place and, for I > J, its transpose through LDS as 512-byte row segments.  Half the
 // MFMA and epilogue work (the kernel is compute-heavy at d = 32: 17.7 us without the kernel
 // evaluation vs 24.5 us, profiles/r04/u), the same output stream.
-template <int DP, int KIND>
+template <int DP, int KIND, class... NV>
 __global__ __launch_bounds__(256) void kmat_mfma_sym(int n, int d, int B, const double* __restrict__ X,
                                                      const double* __restrict__ sh, const double* __restrict__ sc,
                                                      const double* __restrict__ ls, const double* __restrict__ os,
-                                                     const double* __restrict__ dg, double* __restrict__ K) {
+                                                     const double* __restrict__ dg, double* __restrict__ K,
+                                                     NV... nv) {
+  constexpr bool MEMBERS = sizeof...(NV) > 0;
   constexpr int OPS = 2 * DP * (KT + 2), OUT = KT * (KT + 1);
   __shared__ double smem[OPS > OUT ? OPS : OUT];
   double (*As)[KT + 2] = reinterpret_cast<double (*)[KT + 2]>(smem);
@@ -375,6 +394,7 @@ __global__ __launch_bounds__(256) void kmat_mfma_sym(int n, int d, int B, const 
   const int i0 = I * KT, j0 = J * KT;
   const double* lsb = ls + (size_t)b * d;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (MEMBERS) X += (size_t)b * n * d;
   kmat_stage<DP>(As, Bs, X, sh, sc, X, sh, sc, lsb, n, n, d, i0, j0);
   kexp_stage(kexp, tid, 256);
   __syncthreads();
@@ -398,6 +418,18 @@ __global__ __launch_bounds__(256) void kmat_mfma_sym(int n, int d, int B, const 
   const int col = lane & 15, rq = lane >> 4;
   double vals[4][4];
   kmat_epilogue<KIND>(acc, na, nb2, eqr, kexp, wm, wn, I == J, scale, dadd, vals);
+  if constexpr (MEMBERS) {   // the identity on padded rows / columns, before both stores
+    const int nvb = member_nvalid(nv...)[b];
+    if (i0 + KT > nvb) {     // i0 >= j0: only tiles reaching row nvb hold padded entries
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int gi = i0 + wm + (q >> 1) * 16 + rq + 4 * r, gj = j0 + wn + (q & 1) * 16 + col;
+          if (gi >= nvb || gj >= nvb) vals[q][r] = gi == gj ? 1.0 : 0.0;
+        }
+    }
+  }
   kmat_store(Kb, n, n, i0, j0, wm, wn, vals);
   if (I == J) return;
   double (*T)[KT + 1] = reinterpret_cast<double (*)[KT + 1]>(smem);
@@ -583,8 +615,15 @@ int kcross_grad_launch(hipStream_t s, int kind, int B, int n1, int n2, int d, co
 // threads over j, gave 2560 blocks at n = 512, B = 5: two residency rounds, 20.4 us.)  Rows are
 // summed afterwards in a fixed order by colsum_kernel, so the MLL gradient is bitwise
 // reproducible.
+//
+// MEMBERS (evr_kernel_lengthscale_grad_members): member b reads its own inputs X + b n d.  The
+// sum runs over the padded rows and columns as well and needs no nvalid: with the identity
+// padding of evr_kernel_matrix_members the factor's padded block is exactly I, so
+// W = alpha alpha^T - K^-1 is exactly 0 off the diagonal of every padded row and column (its
+// product with the finite dK/dls of the finite padded inputs adds 0), and a diagonal entry has
+// distance 0, i.e. sq[k] = 0: padded entries add exact zeros to the member's own sum.
 constexpr int KLS_ROWS = 4;
-template <int MAXD>
+template <int MAXD, bool MEMBERS = false>
 __global__ __launch_bounds__(256) void kls_grad_kernel(int kind, int n, int d, const double* __restrict__ X,
                                                        const double* __restrict__ ls,
                                                        const double* __restrict__ W, double* __restrict__ part) {
@@ -592,6 +631,7 @@ __global__ __launch_bounds__(256) void kls_grad_kernel(int kind, int n, int d, c
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * KLS_ROWS + (threadIdx.x >> 6);
   if (i >= n) return;   // whole waves (no barrier below)
+  if constexpr (MEMBERS) X += (size_t)b * n * d;
   const double* lsb = ls + (size_t)b * d;
   const double* Wr = W + ((size_t)b * n + i) * n;
   const int kb = kind_of(kind, b);
@@ -644,13 +684,14 @@ __global__ __launch_bounds__(256) void kls_grad_kernel(int kind, int n, int d, c
 
 // Above 16 dims: one block per (row i, output b), 256 threads over j (the wave-per-row form's
 // per-lane (dimension x column) arrays do not stay in registers there).
-template <int MAXD>
+template <int MAXD, bool MEMBERS = false>
 __global__ __launch_bounds__(256) void kls_grad_block_kernel(int kind, int n, int d, const double* __restrict__ X,
                                                        const double* __restrict__ ls,
                                                        const double* __restrict__ W, double* __restrict__ part) {
   const int b = blockIdx.y;
   const int i = blockIdx.x;
   const int tid = threadIdx.x;
+  if constexpr (MEMBERS) X += (size_t)b * n * d;
   const double* lsb = ls + (size_t)b * d;
   const double* Wb = W + (size_t)b * n * n;
   __shared__ double red[256];
@@ -1135,15 +1176,20 @@ long long evr_kernel_cross_grad_workspace_doubles(int n1, int n2, int d) {
   return (n1 > 0 && n2 > 0 && d > 0) ? (long long)kcross_grad_ws_doubles(n1, n2, d) : 0;
 }
 
-int evr_kernel_lengthscale_grad(void* stream, int kind, int B, int n, int d, const double* X,
-                                const double* lengthscales, const double* W, double* gls, double* work) {
-  EVR_CHECK(kind_code_ok(kind, B) && B >= 1 && n >= 1 && d >= 1 && d <= KMAXD,
-            "evr_kernel_lengthscale_grad: bad args");
-  EVR_CHECK(work != nullptr, "evr_kernel_lengthscale_grad: work (B*n*d doubles) required");
-  hipStream_t s = (hipStream_t)stream;
+// evr_kernel_lengthscale_grad and its member form: one dispatch (members: X is B x n x d)
+static int kls_grad_launch(hipStream_t s, bool members, int kind, int B, int n, int d, const double* X,
+                           const double* lengthscales, const double* W, double* gls, double* work) {
   dim3 grid(cdiv(n, KLS_ROWS), B), gridb(n, B);
-#define LAUNCH(MD) kls_grad_kernel<MD><<<grid, 256, 0, s>>>(kind, n, d, X, lengthscales, W, work)
-#define LAUNCHB(MD) kls_grad_block_kernel<MD><<<gridb, 256, 0, s>>>(kind, n, d, X, lengthscales, W, work)
+#define LAUNCH(MD)                                                                                       \
+  do {                                                                                                   \
+    if (members) kls_grad_kernel<MD, true><<<grid, 256, 0, s>>>(kind, n, d, X, lengthscales, W, work);   \
+    else kls_grad_kernel<MD><<<grid, 256, 0, s>>>(kind, n, d, X, lengthscales, W, work);                 \
+  } while (0)
+#define LAUNCHB(MD)                                                                                            \
+  do {                                                                                                         \
+    if (members) kls_grad_block_kernel<MD, true><<<gridb, 256, 0, s>>>(kind, n, d, X, lengthscales, W, work);  \
+    else kls_grad_block_kernel<MD><<<gridb, 256, 0, s>>>(kind, n, d, X, lengthscales, W, work);                \
+  } while (0)
   if (d <= 8) LAUNCH(8);
   else if (d <= 16) LAUNCH(16);
   else if (d <= 32) LAUNCHB(32);
@@ -1152,6 +1198,65 @@ int evr_kernel_lengthscale_grad(void* stream, int kind, int B, int n, int d, con
 #undef LAUNCH
   EVR_LAUNCH_CHECK();
   colsum_kernel<<<B * d, 256, 0, s>>>(B, n, d, work, gls);
+  EVR_LAUNCH_CHECK();
+  return 0;
+}
+
+int evr_kernel_lengthscale_grad(void* stream, int kind, int B, int n, int d, const double* X,
+                                const double* lengthscales, const double* W, double* gls, double* work) {
+  EVR_CHECK(kind_code_ok(kind, B) && B >= 1 && n >= 1 && d >= 1 && d <= KMAXD,
+            "evr_kernel_lengthscale_grad: bad args");
+  EVR_CHECK(work != nullptr, "evr_kernel_lengthscale_grad: work (B*n*d doubles) required");
+  return kls_grad_launch((hipStream_t)stream, false, kind, B, n, d, X, lengthscales, W, gls, work);
+}
+
+int evr_kernel_lengthscale_grad_members(void* stream, int kind, int B, int n, int d, const double* Xb,
+                                        const double* lengthscales, const double* W, double* gls, double* work) {
+  EVR_CHECK(kind >= 0 && kind <= 3 && B >= 1 && n >= 1 && d >= 1 && d <= KMAXD && Xb && lengthscales && W && gls,
+            "evr_kernel_lengthscale_grad_members: bad args");
+  EVR_CHECK(work != nullptr, "evr_kernel_lengthscale_grad_members: work (B*n*d doubles) required");
+  return kls_grad_launch((hipStream_t)stream, true, kind, B, n, d, Xb, lengthscales, W, gls, work);
+}
+
+int evr_kernel_matrix_members(void* stream, int kind, int B, int n, int d, const double* Xb, const int* nvalid,
+                              const double* lengthscales, const double* diag_add, double* K) {
+  EVR_CHECK(kind >= 0 && kind <= 3, "evr_kernel_matrix_members: one kernel family 0..3, got %d", kind);
+  EVR_CHECK(B >= 1 && n >= 1 && d >= 1 && d <= KMAXD && Xb && nvalid && lengthscales && K,
+            "evr_kernel_matrix_members: bad arguments B=%d n=%d d=%d", B, n, d);
+  hipStream_t s = (hipStream_t)stream;
+  const double* none = nullptr;
+  if (d >= 16) {   // kmat_mfma_sym: evr_kernel_matrix's path for the symmetric train matrix
+    const int nt = cdiv(n, KT);
+    const long long tiles = (long long)nt * (nt + 1) / 2 * B;
+#define KS(DP_, K_)                                                                                               \
+  kmat_mfma_sym<DP_, K_, const int*><<<(unsigned)tiles, 256, 0, s>>>(n, d, B, Xb, none, none, lengthscales, none, \
+                                                                     diag_add, K, nvalid)
+#define KSD(DP_)                                \
+  if (kind == RBF) KS(DP_, RBF);                \
+  else if (kind == MATERN05) KS(DP_, MATERN05); \
+  else if (kind == MATERN15) KS(DP_, MATERN15); \
+  else KS(DP_, MATERN25)
+    // (d = 48, which evr_kernel_matrix hands to the cross kernel's 48-column staging, takes the
+    // 64-column symmetric form here: the columns beyond d are zeros, the same values)
+    if (d <= 16) { KSD(16); }
+    else if (d <= 32) { KSD(32); }
+    else { KSD(64); }
+#undef KSD
+#undef KS
+    EVR_LAUNCH_CHECK();
+    return 0;
+  }
+  constexpr int ra = 2;
+  const size_t lds = (size_t)(KT + 16 * ra) * (d + 1) * sizeof(double);
+  dim3 g(cdiv(n, KT), cdiv(n, 16 * ra), B);
+#define KTK(K_)                                                                                                  \
+  kmat_kernel<ra, K_, const int*><<<g, 256, lds, s>>>(kind, n, n, d, Xb, none, none, Xb, none, none, lengthscales, \
+                                                      none, diag_add, K, nullptr, nullptr, nullptr, nullptr, 0, nvalid)
+  if (kind == RBF) KTK(RBF);
+  else if (kind == MATERN05) KTK(MATERN05);
+  else if (kind == MATERN15) KTK(MATERN15);
+  else KTK(MATERN25);
+#undef KTK
   EVR_LAUNCH_CHECK();
   return 0;
 }

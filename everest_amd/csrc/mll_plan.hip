@@ -10,9 +10,17 @@
 // launch cost): at n = 512 the per-evaluation cost of the unfused op chain was ~1.4 ms,
 // mostly launch and synchronisation latency.  A member whose attempt-0 factor fails is
 // reported through info; the caller reruns that evaluation through the jitter ladder.
+//
+// Member plans (evr_mll_plan_create_members: the folds of a cross-validation) run the same
+// chain over B GPs that each have their own inputs and their own number of real rows, padded
+// to a common n with identity rows / columns of K (include/everest_amd.h, member form): the
+// kernel matrix and the lengthscale gradient take their member forms, copy-in zeroes r on the
+// padding, copy-out takes the pad count off tr K^-1, and the host side scales by the
+// member's own size; the factor, the matvecs, W and the terms kernels are used as they are.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -140,21 +148,30 @@ __global__ __launch_bounds__(256) void mll_matvec(int n, const double* __restric
 // hx: [ls (B x d) | noise (B) | constant (B) | sequence number]; also the residuals
 // r = Y - constant (one launch: the constant comes straight from the host buffer, one read
 // per wave since a wave's rows share a member when n >= 64)
+// Member plans (nvalid != nullptr): r = 0 on a member's padded rows i >= nvalid[b].
 __global__ void mll_copy_in(int B, int n, int d, const double* hx, const double* __restrict__ Y, double* ls,
-                            double* noise, double* cst, double* __restrict__ r) {
+                            double* noise, double* cst, double* __restrict__ r, const int* __restrict__ nvalid) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B * d) ls[i] = hx[i];
   if (i < B) {
     noise[i] = hx[B * d + i];
     cst[i] = hx[B * d + B + i];
   }
-  if (i < B * n) r[i] = Y[i] - hx[B * d + B + i / n];
+  if (i < B * n) {
+    const int b = i / n;
+    const double v = Y[i] - hx[B * d + B + b];
+    r[i] = (nvalid && i - b * n >= nvalid[b]) ? 0.0 : v;
+  }
 }
 
 // hout: [terms (B x 5: logdet, r.alpha, tr K^-1, sum alpha, sum alpha^2) | gls (B x d) |
 //        info (B, as doubles) | completion word]; the terms' chunk partials summed in order
+// Member plans (nvalid != nullptr): the identity block of a member's padded rows adds exactly
+// its size n - nvalid[b] to ||L^-1||_F^2 = tr K^-1, taken off here; the other four terms get
+// exact zeros from the padding (log 1, r = alpha = 0).
 __global__ void mll_copy_out(int B, int d, int nch, const double* __restrict__ part, const double* __restrict__ gls,
-                             const int* __restrict__ info, const double* hx, double* hout) {
+                             const int* __restrict__ info, const double* hx, double* hout, int n,
+                             const int* __restrict__ nvalid) {
   const int t = threadIdx.x;
   // one block: every loop strides over blockDim, so any B works (B >= 52 has more than 256 terms)
   for (int e = t; e < B * 5; e += blockDim.x) {
@@ -169,6 +186,7 @@ __global__ void mll_copy_out(int B, int d, int nch, const double* __restrict__ p
       for (int u = 0; u < 32; ++u)
         if (c0 + u < nch) s += v[u];
     }
+    if (nvalid && q == 2) s -= (double)(n - nvalid[b]);
     hout[e] = q == 0 ? 2.0 * s : s;
   }
   for (int i = t; i < B * d; i += blockDim.x) hout[B * 5 + i] = gls[i];
@@ -188,7 +206,9 @@ using namespace evr;
 
 struct evr_mll_plan {
   int kind, B, n, d;
-  const double* Xn;
+  const double* Xn;    // shared inputs (n x d), or the members' (B x n x d) when nvalid is set
+  int* nvalid;         // member plans: real rows per member (device), else nullptr
+  int* nvalid_h;       // its host copy
   double *Y, *ls, *noise, *cst, *K, *L, *Linv, *Dinv, *T, *r, *v, *alpha, *gls, *gw, *part, *jit0;
   int* info;
   double *hx, *hout;
@@ -200,10 +220,12 @@ struct evr_mll_plan {
 static int mll_chain(hipStream_t s, evr_mll_plan* p, const double* dhx, double* dhout) {
   const int B = p->B, n = p->n, d = p->d;
   mll_copy_in<<<cdiv(std::max(B * d + B, B * n), 256), 256, 0, s>>>(B, n, d, dhx, p->Y, p->ls, p->noise, p->cst,
-                                                                       p->r);
+                                                                       p->r, p->nvalid);
   EVR_LAUNCH_CHECK();
-  if (int rc = evr_kernel_matrix(s, p->kind, B, n, n, d, p->Xn, nullptr, nullptr, p->Xn, nullptr, nullptr, p->ls,
-                                 nullptr, p->noise, p->K))
+  if (p->nvalid) {
+    if (int rc = evr_kernel_matrix_members(s, p->kind, B, n, d, p->Xn, p->nvalid, p->ls, p->noise, p->K)) return rc;
+  } else if (int rc = evr_kernel_matrix(s, p->kind, B, n, n, d, p->Xn, nullptr, nullptr, p->Xn, nullptr, nullptr,
+                                        p->ls, nullptr, p->noise, p->K))
     return rc;
   if (int rc = chol_inverse_attempt(s, B, n, p->K, p->L, p->Linv, p->Dinv, p->T, p->jit0, p->info)) return rc;
   double* W = p->K;   // K was consumed by the factorisation
@@ -218,9 +240,12 @@ static int mll_chain(hipStream_t s, evr_mll_plan* p, const double* dhx, double* 
     else mll_w_kernel<false><<<lower * B, 256, 0, s>>>(n, B, p->Linv, p->alpha, W);
     EVR_LAUNCH_CHECK();
   }
-  if (int rc = evr_kernel_lengthscale_grad(s, p->kind, B, n, d, p->Xn, p->ls, W, p->gls, p->gw)) return rc;
+  if (p->nvalid) {
+    if (int rc = evr_kernel_lengthscale_grad_members(s, p->kind, B, n, d, p->Xn, p->ls, W, p->gls, p->gw)) return rc;
+  } else if (int rc = evr_kernel_lengthscale_grad(s, p->kind, B, n, d, p->Xn, p->ls, W, p->gls, p->gw))
+    return rc;
   if (int rc = mll_terms_partials(s, B, n, p->L, p->Linv, p->r, p->alpha, p->part)) return rc;
-  mll_copy_out<<<1, 256, 0, s>>>(B, d, mll_terms_chunks(), p->part, p->gls, p->info, dhx, dhout);
+  mll_copy_out<<<1, 256, 0, s>>>(B, d, mll_terms_chunks(), p->part, p->gls, p->info, dhx, dhout, n, p->nvalid);
   EVR_LAUNCH_CHECK();
   return 0;
 }
@@ -234,17 +259,22 @@ static void mll_free(evr_mll_plan* p) {
   for (double* b : bufs)
     if (b) (void)hipFree(b);
   if (p->info) (void)hipFree(p->info);
+  if (p->nvalid) (void)hipFree(p->nvalid);
+  std::free(p->nvalid_h);
   if (p->hx) (void)hipHostFree(p->hx);
   if (p->hout) (void)hipHostFree(p->hout);
   delete p;
 }
 
-extern "C" {
-
-int evr_mll_plan_create(void* stream, int kind, int B, int n, int d, const double* Xn, const double* Y,
-                        evr_mll_plan** out) {
+// evr_mll_plan_create (nvalid == nullptr: Xn n x d, shared) and evr_mll_plan_create_members
+// (nvalid: B host counts in 1..n; Xn B x n x d)
+static int mll_plan_create(void* stream, int kind, int B, int n, int d, const double* Xn, const double* Y,
+                           const int* nvalid, evr_mll_plan** out) {
   EVR_CHECK(out && Xn && Y && B >= 1 && n >= 1 && d >= 1 && kind >= 0 && kind <= 3,
             "evr_mll_plan_create: bad arguments");
+  for (int b = 0; nvalid && b < B; ++b)
+    EVR_CHECK(nvalid[b] >= 1 && nvalid[b] <= n, "evr_mll_plan_create_members: nvalid[%d] = %d outside 1..%d", b,
+              nvalid[b], n);
   evr_mll_plan* p = new (std::nothrow) evr_mll_plan();
   EVR_CHECK(p, "evr_mll_plan_create: out of host memory");
   std::memset((void*)p, 0, sizeof(*p));
@@ -268,6 +298,15 @@ int evr_mll_plan_create(void* stream, int kind, int B, int n, int d, const doubl
       mll_free(p);
       EVR_CHECK(false, "evr_mll_plan_create: device allocation failed");
     }
+  }
+  if (nvalid) {
+    p->nvalid_h = (int*)std::malloc(sizeof(int) * B);
+    if (!p->nvalid_h || hipMalloc((void**)&p->nvalid, sizeof(int) * B) != hipSuccess ||
+        hipMemcpy(p->nvalid, nvalid, sizeof(int) * B, hipMemcpyHostToDevice) != hipSuccess) {
+      mll_free(p);
+      EVR_CHECK(false, "evr_mll_plan_create_members: allocation failed");
+    }
+    std::memcpy(p->nvalid_h, nvalid, sizeof(int) * B);
   }
   if (hipMalloc((void**)&p->info, sizeof(int) * B) != hipSuccess ||
       hipHostMalloc((void**)&p->hx, sizeof(double) * ((size_t)B * (d + 2) + 1),
@@ -311,6 +350,19 @@ int evr_mll_plan_create(void* stream, int kind, int B, int n, int d, const doubl
   }
   *out = p;
   return 0;
+}
+
+extern "C" {
+
+int evr_mll_plan_create(void* stream, int kind, int B, int n, int d, const double* Xn, const double* Y,
+                        evr_mll_plan** out) {
+  return mll_plan_create(stream, kind, B, n, d, Xn, Y, nullptr, out);
+}
+
+int evr_mll_plan_create_members(void* stream, int kind, int B, int n, int d, const double* Xb, const double* Y,
+                                const int* nvalid, evr_mll_plan** out) {
+  EVR_CHECK(nvalid, "evr_mll_plan_create_members: nvalid required");
+  return mll_plan_create(stream, kind, B, n, d, Xb, Y, nvalid, out);
 }
 
 int evr_mll_plan_eval(void* stream, evr_mll_plan* p, const double* params, double* out) {
@@ -433,6 +485,18 @@ int evr_mll_assemble(int B, int n, int d, const double* prior, const double* x, 
   return 0;
 }
 
+int evr_mll_assemble_members(int B, const int* nvalid, int d, const double* prior, const double* x,
+                             const double* terms, const double* gls, double* ll, double* g) {
+  EVR_CHECK(B >= 0 && nvalid && d >= 1 && prior && x && terms && gls && ll && g,
+            "evr_mll_assemble_members: bad arguments");
+  for (int b = 0; b < B; ++b) {
+    EVR_CHECK(nvalid[b] >= 1, "evr_mll_assemble_members: nvalid[%d] = %d", b, nvalid[b]);
+    mll_assemble_one(nvalid[b], d, prior, x + (size_t)b * (d + 2), terms + (size_t)b * 5, gls + (size_t)b * d, ll + b,
+                     g + (size_t)b * (d + 2));
+  }
+  return 0;
+}
+
 int evr_mll_fit_rounds(void* stream, evr_mll_plan* p, void** runs, int* task, double* x, double* f, double* g,
                        int* nit, int* nfev, int* status, int maxiter, int maxfun, const double* prior, double* params,
                        int* pending) {
@@ -469,7 +533,9 @@ int evr_mll_fit_rounds(void* stream, evr_mll_plan* p, void** runs, int* task, do
       if (task[b] != EVR_LBFGSB_FG) continue;
       double* xb = x + (size_t)b * nx;
       double llb;
-      mll_assemble_one(n, d, prior, xb, terms + (size_t)b * 5, gls + (size_t)b * d, &llb, gb.data());
+      // a member plan's member is scaled by its own size
+      mll_assemble_one(p->nvalid_h ? p->nvalid_h[b] : n, d, prior, xb, terms + (size_t)b * 5, gls + (size_t)b * d,
+                       &llb, gb.data());
       // minimise -MLL / n
       f[b] = -llb;
       for (int j = 0; j < nx; ++j) g[(size_t)b * nx + j] = -gb[j];

@@ -277,8 +277,12 @@ __global__ __launch_bounds__(256, 4) void qn_proj_bwd(int n, int nb, int nh, int
   const double* cj = coef + (size_t)j * 3 * b;
   const double aj = oa[j];
   const int kbeg = kz * kchunk, kend = min(Rr, kbeg + kchunk);
+  // k < Rr: a segment's last 16-deep k-step runs past its end, where the other operand is 0.
+  // Rows of M below Rr are finite (0 x finite = 0, the value as before), but past the last
+  // output's M lies whatever memory follows it: a stale NaN there made the whole tile NaN
   auto fa = [&](int k, int c) -> dg_double2 {
-    return dg_pair<VEC>(A + (size_t)k * n + m0 + c, m0 + c < n, m0 + c + 1 < n);
+    const bool ok = k < Rr;
+    return dg_pair<VEC>(A + (size_t)k * n + m0 + c, ok && m0 + c < n, ok && m0 + c + 1 < n);
   };
   // class segments of this slice: [lo, hi) of rows < n, [n, n + nb), the sample rows
   dg_double4 a0[C::FM][C::FN], a1[C::FM][C::FN], a2[C::FM][C::FN];

@@ -325,41 +325,80 @@ class MLLBatch:
     evaluated for any subset of the outputs in one batched launch chain (kernel matrices,
     psd_safe Cholesky + inverse, alpha, W = alpha alpha^T - K^-1, lengthscale gradients, the
     scalar terms) and one device->host copy.  Returns None for a member whose Cholesky stays
-    not p.d. after the jitter ladder (NotPSDError of that fit)."""
+    not p.d. after the jitter ladder (NotPSDError of that fit).
 
-    def __init__(self, Xn: torch.Tensor, Ys: np.ndarray, kind: int, ls_prior, noise_prior):
+    Member form (``nvalid`` given): member b has its own inputs ``Xn[b]`` (Xn is B x n x d) of
+    which the first ``nvalid[b]`` rows are real; the rest is padding (zeros) that the member
+    kernels turn into identity rows / columns of K (include/everest_amd.h, member form), and
+    every value is that of the member's own GP on its own rows, MLL / nvalid[b]."""
+
+    def __init__(self, Xn: torch.Tensor, Ys: np.ndarray, kind: int, ls_prior, noise_prior, nvalid=None):
         self.Xn = Xn.contiguous()
-        self.n, self.d = Xn.shape
+        self.n, self.d = Xn.shape[-2:]
         self.kind = kind
         self.Y = torch.as_tensor(np.asarray(Ys, dtype=np.float64), device=Xn.device)   # B x n (standardized)
         self.ls_prior = _prior(ls_prior)
         self.noise_prior = _prior(noise_prior)
         self.use_plan = os.environ.get("EVR_MLL_PLAN", "1") != "0"
         self._plan = None
+        self.nvalid = None
+        if nvalid is not None:
+            self.nvalid = np.ascontiguousarray(nvalid, dtype=np.int32)
+            if self.Xn.dim() != 3 or self.nvalid.shape != (self.Xn.shape[0],) or self.Y.shape != self.Xn.shape[:2]:
+                raise ValueError(f"members: Xn {tuple(self.Xn.shape)} (B x n x d), Y {tuple(self.Y.shape)} (B x n) "
+                                 f"and nvalid {self.nvalid.shape} (B) do not match")
+            if self.nvalid.min() < 1 or self.nvalid.max() > self.n:
+                raise ValueError(f"members: nvalid must lie in 1..{self.n}")
+            self._nvalid_t = torch.as_tensor(self.nvalid, device=Xn.device)
+            # 1 on a member's real rows, 0 on its padding
+            self._real = (torch.arange(self.n, device=Xn.device)[None, :] < self._nvalid_t[:, None]).to(torch.float64)
 
     def _eval_ops(self, idx, ls, noise, const):
         """The op-by-op chain with the psd_safe_cholesky jitter ladder (host arrays)."""
         dev = self.Xn.device
         ls_t = torch.as_tensor(ls, device=dev)
-        Ky = ops.kernel_matrix(self.Xn, self.Xn, ls_t, self.kind, diag_add=torch.as_tensor(noise, device=dev))
-        L, Linv, _, info = ops.cholesky_inverse(Ky, 1e-8, 3, raise_on_fail=False)
         it = torch.as_tensor(np.asarray(idx, dtype=np.int64), device=dev)
-        r = (self.Y[it] - torch.as_tensor(const, device=dev)[:, None]).unsqueeze(-1).contiguous()   # B x n x 1
+        members = self.nvalid is not None
+        if members:
+            Xb, real = self.Xn[it].contiguous(), self._real[it]
+            Ky = ops.kernel_matrix_members(Xb, self._nvalid_t[it].contiguous(), ls_t, self.kind,
+                                           diag_add=torch.as_tensor(noise, device=dev))
+        else:
+            Ky = ops.kernel_matrix(self.Xn, self.Xn, ls_t, self.kind, diag_add=torch.as_tensor(noise, device=dev))
+        L, Linv, _, info = ops.cholesky_inverse(Ky, 1e-8, 3, raise_on_fail=False)
+        r = self.Y[it] - torch.as_tensor(const, device=dev)[:, None]
+        if members:
+            r = r * real                                                     # r = 0 on padded rows
+        r = r.unsqueeze(-1).contiguous()                                     # B x n x 1
         v = ops.gemm(Linv, r)
         alpha = ops.gemm(Linv, v, transA=True)
         W = ops.gemm(alpha, alpha, transB=True)
         ops.gemm(Linv, Linv, transA=True, alpha=-1.0, beta=1.0, out=W)
-        gls = ops.kernel_lengthscale_grad(self.Xn, ls_t, W, self.kind)
+        if members:
+            gls = ops.kernel_lengthscale_grad_members(Xb, ls_t, W, self.kind)
+        else:
+            gls = ops.kernel_lengthscale_grad(self.Xn, ls_t, W, self.kind)
         terms = ops.mll_terms(L, Linv, r[..., 0].contiguous(), alpha[..., 0].contiguous())
+        if members:
+            # the padded block of the factor is sqrt(1 + jitter) I (jitter 0 unless the ladder was
+            # climbed): its share of log det and of tr K^-1 = ||L^-1||_F^2 is taken off exactly;
+            # r.alpha, sum alpha and sum alpha^2 get zeros from it
+            pad = 1.0 - real
+            terms[:, 0] -= 2.0 * (torch.log(L.diagonal(dim1=-2, dim2=-1)) * pad).sum(1)
+            terms[:, 2] -= (Linv.diagonal(dim1=-2, dim2=-1) ** 2 * pad).sum(1)
         return torch.cat([terms.reshape(-1), gls.reshape(-1), info.to(torch.float64)]).cpu().numpy()
 
     def plan_handle(self):
-        """The native MLL plan (evr_mll_plan_create), built on first use."""
+        """The native MLL plan (evr_mll_plan_create[_members]), built on first use."""
         if self._plan is None:
             Bt, d = self.Y.shape[0], self.d
             h = ctypes.c_void_p()
-            ops.call("evr_mll_plan_create", ops._stream(), int(self.kind), Bt, self.n, d, self.Xn.data_ptr(),
-                     self.Y.data_ptr(), ctypes.byref(h))
+            if self.nvalid is not None:
+                ops.call("evr_mll_plan_create_members", ops._stream(), int(self.kind), Bt, self.n, d,
+                         self.Xn.data_ptr(), self.Y.data_ptr(), self.nvalid.ctypes.data, ctypes.byref(h))
+            else:
+                ops.call("evr_mll_plan_create", ops._stream(), int(self.kind), Bt, self.n, d, self.Xn.data_ptr(),
+                         self.Y.data_ptr(), ctypes.byref(h))
             self._plan = h
             self._lib = _native.load()
             self._params = None
@@ -427,8 +466,15 @@ class MLLBatch:
         ll = np.empty(B)
         g = np.empty((B, d + 2))
         lib = _native.load()
-        _native.check(lib.evr_mll_assemble(B, n, d, self.prior_spec().ctypes.data, xs.ctypes.data, terms_h.ctypes.data,
-                                           gls_h.ctypes.data, ll.ctypes.data, g.ctypes.data), "evr_mll_assemble")
+        if self.nvalid is not None:      # member b's own size in the -n/2 log 2 pi term and the 1 / n
+            nv = np.ascontiguousarray(self.nvalid[np.asarray(idx, dtype=np.int64)])
+            _native.check(lib.evr_mll_assemble_members(B, nv.ctypes.data, d, self.prior_spec().ctypes.data,
+                                                       xs.ctypes.data, terms_h.ctypes.data, gls_h.ctypes.data,
+                                                       ll.ctypes.data, g.ctypes.data), "evr_mll_assemble_members")
+        else:
+            _native.check(lib.evr_mll_assemble(B, n, d, self.prior_spec().ctypes.data, xs.ctypes.data,
+                                               terms_h.ctypes.data, gls_h.ctypes.data, ll.ctypes.data,
+                                               g.ctypes.data), "evr_mll_assemble")
         return [None if info_h[k] != 0 or not np.all(np.isfinite(terms_h[k])) else (float(ll[k]), g[k].copy())
                 for k in range(B)]
 
@@ -520,12 +566,8 @@ def fit_batch(Xn: torch.Tensor, Y_raw: np.ndarray, kind: int, ls_prior, noise_pr
     evaluates the outputs that asked for a function value in ONE batched MLL launch chain.
     The fits stay independent problems, as in the reference's per-surrogate
     fit_gpytorch_mll (bofire/surrogates/single_task_gp.py:70-71)."""
-    from .optim import lbfgsb_steps
-
     Y_raw = np.asarray(Y_raw, dtype=np.float64).reshape(Xn.shape[0], -1)
-    B, d = Y_raw.shape[1], Xn.shape[1]
-    opts = dict(options or {})
-    maxiter, maxfun = int(opts.get("maxiter", 15000)), int(opts.get("maxfun", 15000))
+    B = Y_raw.shape[1]
     stats, Ys = [], []
     for b in range(B):
         ym, ys = standardize_params(Y_raw[:, b]) if standardize else (0.0, 1.0)
@@ -533,6 +575,18 @@ def fit_batch(Xn: torch.Tensor, Y_raw: np.ndarray, kind: int, ls_prior, noise_pr
         Ys.append((Y_raw[:, b] - ym) / ys)
     lsp, nzp = _prior(ls_prior), _prior(noise_prior)
     ev = MLLBatch(Xn, np.stack(Ys), kind, lsp, nzp)
+    return _fit_lockstep(ev, stats, max_attempts, seed, options)
+
+
+def _fit_lockstep(ev: MLLBatch, stats, max_attempts: int, seed: int, options: Optional[dict]) -> List[GPHyper]:
+    """The lock-step L-BFGS-B loop of fit_batch / fit_folds over the members of ``ev`` (shared
+    inputs or member form alike); ``stats``: each member's (y_mean, y_std)."""
+    from .optim import lbfgsb_steps
+
+    B, d = ev.Y.shape[0], ev.d
+    lsp, nzp = ev.ls_prior, ev.noise_prior
+    opts = dict(options or {})
+    maxiter, maxfun = int(opts.get("maxiter", 15000)), int(opts.get("maxfun", 15000))
     if nzp is not None and nzp[0] == "lognormal":
         noise0 = math.exp(nzp[1] - nzp[2] ** 2)
     elif nzp is not None and nzp[0] == "gamma" and nzp[1] > 1:
@@ -584,3 +638,63 @@ def fit_batch(Xn: torch.Tensor, Y_raw: np.ndarray, kind: int, ls_prior, noise_pr
     LAST_FIT_STATS.update(driver="python", nfev=[counts[b][0] for b in range(B)], nit=[counts[b][1] for b in range(B)])
     return [GPHyper(lengthscale=softplus_np(result[b][2:]), noise=float(result[b][0]), constant=float(result[b][1]),
                     y_mean=stats[b][0], y_std=stats[b][1]) for b in range(B)]
+
+
+# ---------------------------------------------------------------------------------------
+# lock-step fit of members on their own rows: the folds of a cross-validation
+# ---------------------------------------------------------------------------------------
+# Cap on the device workspace of one member plan (evr_mll_plan_create_members), in bytes: more
+# members than fit under it are fitted chunk after chunk.  A memory bound, not a tuning knob.
+CV_PLAN_BYTES = 2 << 30
+
+
+def plan_member_bytes(n: int, d: int) -> int:
+    """Device bytes of one member of an MLL plan over n rows and d inputs: K, L and L^-1
+    (3 n^2), the factorisation's 64-row panel (64 n), the lengthscale-gradient partials (n d),
+    the member's inputs (n d) and its n-vectors (Y, r, v, alpha and the block inverses' share)."""
+    return 8 * (3 * n * n + 64 * n + 2 * n * d + 8 * n)
+
+
+def member_chunks(B: int, n: int, d: int) -> List[range]:
+    """Consecutive member ranges whose plans stay under CV_PLAN_BYTES (at least one member each)."""
+    per = max(1, CV_PLAN_BYTES // plan_member_bytes(n, d))
+    return [range(b0, min(B, b0 + per)) for b0 in range(0, B, per)]
+
+
+def fit_folds(Xb, Y_raw_b: np.ndarray, nvalid, kind: int, ls_prior, noise_prior, standardize: bool,
+              max_attempts: int = 10, seed: int = 0, options: Optional[dict] = None) -> List[GPHyper]:
+    """fit_batch for B members that each train on their own rows (the folds of
+    SingleTaskGPSurrogate.cross_validate): member b has the normalised inputs ``Xb[b]``
+    (B x nmax x d, device; rows >= ``nvalid[b]`` are padding and must be zeros) and the raw
+    targets ``Y_raw_b[b, :nvalid[b]]``, standardised here with its own statistics.  The same
+    lock-step loop, start point, bounds and restarts as fit_batch, over a member MLL plan;
+    the members are split into chunks of at most CV_PLAN_BYTES of plan workspace, fitted one
+    chunk after another (independent problems: a member's fit does not depend on its chunk
+    beyond batched-kernel rounding).  LAST_FIT_STATS holds all members' counts."""
+    Xb = torch.as_tensor(Xb, dtype=torch.float64)
+    if Xb.device.type != "cuda":
+        Xb = Xb.to(torch.device("cuda", torch.cuda.current_device()))
+    Xb = Xb.contiguous()
+    nvalid = np.asarray(nvalid, dtype=np.int32)
+    Y_raw_b = np.asarray(Y_raw_b, dtype=np.float64)
+    B, n, d = Xb.shape
+    if Y_raw_b.shape != (B, n) or nvalid.shape != (B,) or nvalid.min() < 1 or nvalid.max() > n:
+        raise ValueError(f"fit_folds: Xb {tuple(Xb.shape)}, Y {Y_raw_b.shape}, nvalid {nvalid.shape} do not match")
+    stats, Ys = [], np.zeros((B, n))
+    for b in range(B):
+        yb = Y_raw_b[b, :nvalid[b]]
+        ym, ys = standardize_params(yb) if standardize else (0.0, 1.0)
+        stats.append((ym, ys))
+        Ys[b, :nvalid[b]] = (yb - ym) / ys
+    lsp, nzp = _prior(ls_prior), _prior(noise_prior)
+    hypers, nfev, nit, driver = [], [], [], None
+    for ch in member_chunks(B, n, d):
+        sl = slice(ch.start, ch.stop)
+        ev = MLLBatch(Xb[sl], Ys[sl], kind, lsp, nzp, nvalid=nvalid[sl])
+        hypers += _fit_lockstep(ev, stats[sl], max_attempts, seed, options)
+        nfev += LAST_FIT_STATS["nfev"]
+        nit += LAST_FIT_STATS["nit"]
+        driver = LAST_FIT_STATS["driver"]
+        del ev          # the chunk's plan is freed before the next one is built
+    LAST_FIT_STATS.update(driver=driver, nfev=nfev, nit=nit)
+    return hypers

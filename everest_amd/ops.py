@@ -106,6 +106,44 @@ def kernel_lengthscale_grad(X, lengthscales, W, kind=0) -> torch.Tensor:
     return g
 
 
+def _members(Xb, lengthscales, nvalid=None):
+    Xb, ls = _dev(Xb, "Xb"), _dev(lengthscales, "lengthscales")
+    if Xb.dim() != 3 or ls.dim() != 2 or ls.shape[0] != Xb.shape[0] or ls.shape[1] != Xb.shape[2]:
+        raise ValueError(f"members: Xb {tuple(Xb.shape)} must be B x n x d and ls {tuple(ls.shape)} B x d")
+    if nvalid is not None:
+        nvalid = _dev(nvalid, "nvalid", torch.int32)
+        if tuple(nvalid.shape) != (Xb.shape[0],):
+            raise ValueError(f"members: nvalid {tuple(nvalid.shape)} must hold one count per member")
+    return Xb, ls, nvalid
+
+
+def kernel_matrix_members(Xb, nvalid, lengthscales, kind: int = 0, diag_add=None) -> torch.Tensor:
+    """Train matrices of B members on their own rows (evr_kernel_matrix_members): Xb B x n x d,
+    nvalid (B, int32, device; counts in 1..n are the caller's to guarantee) the real rows of
+    each; padded rows / columns are the identity."""
+    Xb, ls, nvalid = _members(Xb, lengthscales, nvalid)
+    B, n, d = Xb.shape
+    K = torch.empty(B, n, n, dtype=torch.float64, device=Xb.device)
+    dg = None if diag_add is None else _dev(diag_add, "diag_add")
+    call("evr_kernel_matrix_members", _stream(), int(kind), B, n, d, Xb.data_ptr(), nvalid.data_ptr(), ls.data_ptr(),
+         _p(dg), K.data_ptr())
+    return K
+
+
+def kernel_lengthscale_grad_members(Xb, lengthscales, W, kind=0) -> torch.Tensor:
+    """kernel_lengthscale_grad with member b on its own inputs Xb[b] (B x n x d)."""
+    Xb, ls, _ = _members(Xb, lengthscales)
+    W = _dev(W, "W")
+    B, n, d = Xb.shape
+    if tuple(W.shape) != (B, n, n):
+        raise ValueError(f"kernel_lengthscale_grad_members: W shape {tuple(W.shape)} != {(B, n, n)}")
+    g = torch.empty(B, d, dtype=torch.float64, device=Xb.device)
+    work = torch.empty(B, n, d, dtype=torch.float64, device=Xb.device)
+    call("evr_kernel_lengthscale_grad_members", _stream(), int(kind), B, n, d, Xb.data_ptr(), ls.data_ptr(),
+         W.data_ptr(), g.data_ptr(), work.data_ptr())
+    return g
+
+
 def mll_terms(L, Linv, r, alpha) -> torch.Tensor:
     """B x 5: logdet, quad, tr(K^-1), sum(alpha), sum(alpha^2)."""
     L, Linv, r, alpha = _dev(L, "L"), _dev(Linv, "Linv"), _dev(r, "r"), _dev(alpha, "alpha")

@@ -9,10 +9,13 @@ which cannot be produced without BoTorch.
 from __future__ import annotations
 
 import base64
+import copy
 import io
 import json
 import math
-from typing import Dict, List, Optional, Tuple
+import os
+import warnings
+from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import pandas as pd
@@ -21,9 +24,64 @@ import torch
 from . import data_models as dm
 from .data_models.models import (CategoricalEncodingEnum, DimensionalityScaledLogNormalPrior, GammaPrior,
                                   LogNormalPrior, MaternKernel, NormalPrior, RBFKernel, ScalerEnum)
+from .diagnostics import CvResult, CvResults
 from .gp import GPBatch, GPHyper, fit_single, standardize_params
 
 KIND_BY_NU = {0.5: 1, 1.5: 2, 2.5: 3}
+# feature types a cross-validation can be stratified by (of the reference's DiscreteInput,
+# CategoricalInput, CategoricalOutput and ContinuousOutput, the ones this build has)
+_STRATIFIABLE = (dm.CategoricalInput, dm.ContinuousOutput)
+
+
+def check_valid_nfolds(folds: int, n: int) -> int:
+    """The number of folds to run on n experiments (trainable.py:270-295): -1 is leave-one-out,
+    more folds than experiments falls back to it with a warning."""
+    if n == 0:
+        raise ValueError("Experiments is empty.")
+    if folds > n:
+        warnings.warn(f"Training data only has {n} experiments, which is less than folds, fallback to LOOCV.")
+        return n
+    if folds == -1:
+        return n
+    if folds < 2:
+        raise ValueError("Folds must be -1 for LOO, or > 1.")
+    return folds
+
+
+def kfold_indices(n: int, k: int, random_state: Optional[int] = None) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """(train, test) index arrays of ``sklearn.model_selection.KFold(k, shuffle=True,
+    random_state=random_state).split`` on n rows, restated in numpy: one shuffle of range(n)
+    by RandomState(random_state), cut into consecutive slices of n // k rows (one more in the
+    first n % k); a fold's test rows are its slice, sorted, its train rows the others, ascending."""
+    idx = np.arange(n)
+    np.random.RandomState(random_state).shuffle(idx)
+    sizes = np.full(k, n // k, dtype=int)
+    sizes[:n % k] += 1
+    out, start = [], 0
+    for size in sizes:
+        held = np.zeros(n, dtype=bool)
+        held[idx[start:start + size]] = True
+        out.append((np.flatnonzero(~held), np.flatnonzero(held)))
+        start += size
+    return out
+
+
+def cv_splits(experiments: pd.DataFrame, folds: int, random_state: Optional[int] = None,
+              stratified_feature: Optional[str] = None, group_split_column: Optional[str] = None):
+    """The folds' (train, test) row positions (trainable.py:297-339): stratified K-fold when a
+    feature is named, else group shuffle splits when a group column is, else shuffled K-fold."""
+    if stratified_feature is None and group_split_column is None:
+        return kfold_indices(len(experiments), folds, random_state)
+    try:
+        from sklearn.model_selection import GroupShuffleSplit, StratifiedKFold
+    except ImportError as e:
+        raise NotImplementedError("stratified and group splits need the scikit-learn package (sklearn), "
+                                  "which is not installed") from e
+    if stratified_feature is not None:
+        cv = StratifiedKFold(n_splits=folds, shuffle=True, random_state=random_state)
+        return list(cv.split(experiments.drop([stratified_feature], axis=1), experiments[stratified_feature]))
+    cv = GroupShuffleSplit(n_splits=folds, random_state=random_state)
+    return list(cv.split(experiments, groups=experiments[group_split_column]))
 
 
 def device() -> torch.device:
@@ -108,12 +166,17 @@ class SingleTaskGPSurrogate:
         X, Y = self._fit_data(experiments)
         self._fit(X, Y, options)
 
-    def _fit_data(self, experiments: pd.DataFrame):
+    def _preprocess_experiments(self, experiments: pd.DataFrame) -> pd.DataFrame:
+        """The rows valid for this output (bofire/surrogates/trainable.py:44-66), all columns."""
         key = self.output_key
         df = experiments
         if f"valid_{key}" in df:
             df = df[df[f"valid_{key}"] > 0]
-        df = df.dropna(subset=[key])
+        return df.dropna(subset=[key])
+
+    def _fit_data(self, experiments: pd.DataFrame):
+        key = self.output_key
+        df = self._preprocess_experiments(experiments)
         return df[self.inputs.get_keys()], df[[key]]
 
     def _fit_problem(self, X: pd.DataFrame, Y: pd.DataFrame) -> dict:
@@ -161,6 +224,131 @@ class SingleTaskGPSurrogate:
         key = self.output_key
         return pd.DataFrame({f"{key}_pred": mean[0].cpu().numpy(), f"{key}_sd": np.sqrt(var[0].cpu().numpy())},
                             index=experiments.index)
+
+    # ---- cross-validation --------------------------------------------------------------
+    def cross_validate(self, experiments: pd.DataFrame, folds: int = -1, include_X: bool = False,
+                       include_labcodes: bool = False, random_state: Optional[int] = None,
+                       stratified_feature: Optional[str] = None, group_split_column: Optional[str] = None,
+                       hooks: Optional[Dict[str, Callable]] = None,
+                       hook_kwargs: Optional[Dict[str, Dict[str, Any]]] = None
+                       ) -> Tuple[CvResults, CvResults, Dict[str, list]]:
+        """TrainableSurrogate.cross_validate (bofire/surrogates/trainable.py:79-339): K-fold (or,
+        folds = -1, leave-one-out) cross-validation on the rows valid for this output.  Returns
+        the folds' train results, their test results, and per hook the list of its return
+        values (a hook is called once per fold as ``hook(surrogate=, X_train=, y_train=,
+        X_test=, y_test=, **hook_kwargs[name])`` with a surrogate fitted on that fold).
+
+        Every fold is its own fit on its own rows, with its own Normalize bounds and Standardize
+        statistics, as in the reference's loop of ``_fit`` calls — but the folds are fitted in
+        lock-step (gp.fit_folds: one L-BFGS-B per fold, one member MLL plan launch per round) and
+        predicted by one masked GPBatch posterior over all rows (fold j is output j, its mask
+        its train rows, its bounds folded into its lengthscales as in
+        BotorchSurrogates.compatibilize).  EVR_CV_LOCKSTEP=0 runs the plain sequential loop
+        (a fresh surrogate per fold: ``_fit``, then ``predict`` twice).
+
+        Unlike the reference, which leaves the last fold's model in ``self``, this surrogate's own
+        fitted state is left as it was.  Plain K-fold splits are those of
+        ``sklearn.model_selection.KFold(shuffle=True, random_state=random_state)`` (kfold_indices);
+        ``stratified_feature`` and ``group_split_column`` need scikit-learn."""
+        if include_labcodes and "labcode" not in experiments.columns:
+            raise ValueError("No labcodes available for the provided experiments.")
+        if len(self.outputs) > 1:
+            raise NotImplementedError("Cross validation not implemented for multi-output models")
+        if stratified_feature is not None:
+            if stratified_feature not in self.inputs.get_keys() + self.outputs.get_keys():
+                raise ValueError("The feature to be stratified is not in the model inputs or outputs")
+            feats = self.inputs if stratified_feature in self.inputs.get_keys() else self.outputs
+            if not isinstance(feats.get_by_key(stratified_feature), _STRATIFIABLE):
+                raise ValueError("The feature to be stratified needs to be a DiscreteInput, CategoricalInput, "
+                                 "CategoricalOutput, or ContinuousOutput")
+        if group_split_column is not None:
+            if group_split_column not in experiments.columns:
+                raise ValueError(f"Group split column {group_split_column} is not present in the experiments.")
+            ngroups = experiments[group_split_column].nunique(dropna=False)
+            if ngroups < folds:
+                raise ValueError(f"Number of unique groups {ngroups} is less than the number of folds {folds}.")
+        experiments = self._preprocess_experiments(experiments)
+        folds = check_valid_nfolds(folds, len(experiments))
+        splits = cv_splits(experiments, folds, random_state, stratified_feature, group_split_column)
+        hooks, hook_kwargs = hooks or {}, hook_kwargs or {}
+        key, in_keys = self.output_key, self.inputs.get_keys()
+        lockstep = os.environ.get("EVR_CV_LOCKSTEP", "1") != "0"
+        fitted = self._cv_lockstep(experiments, splits) if lockstep else self._cv_sequential(experiments, splits)
+        train_results, test_results, hook_results = [], [], {name: [] for name in hooks}
+        for (tr, te), (surrogate, pred) in zip(splits, fitted):
+            rows = {"train": experiments.iloc[tr], "test": experiments.iloc[te]}
+            for part, out in (("train", train_results), ("test", test_results)):
+                df = rows[part]
+                out.append(CvResult(key=key, observed=df[key], predicted=pred[part][f"{key}_pred"],
+                                    standard_deviation=pred[part][f"{key}_sd"],
+                                    X=df[in_keys] if include_X else None,
+                                    labcodes=df["labcode"] if include_labcodes else None))
+            fold_model = surrogate() if hooks else None      # built only when a hook asks for it
+            for name, hook in hooks.items():
+                hook_results[name].append(hook(surrogate=fold_model, X_train=rows["train"][in_keys],
+                                               y_train=rows["train"][[key]], X_test=rows["test"][in_keys],
+                                               y_test=rows["test"][[key]], **hook_kwargs.get(name, {})))
+        return CvResults(train_results), CvResults(test_results), hook_results
+
+    def _cv_sequential(self, experiments: pd.DataFrame, splits):
+        """Per fold (surrogate getter, {"train" / "test": predictions}): one fit after another."""
+        key, in_keys = self.output_key, self.inputs.get_keys()
+        out = []
+        for tr, te in splits:
+            sur = copy.copy(self)
+            sur._fit(experiments.iloc[tr][in_keys], experiments.iloc[tr][[key]])
+            out.append((lambda s=sur: s, {"train": sur.predict(experiments.iloc[tr][in_keys]),
+                                          "test": sur.predict(experiments.iloc[te][in_keys])}))
+        return out
+
+    def _cv_lockstep(self, experiments: pd.DataFrame, splits):
+        """_cv_sequential's result with all folds fitted in lock-step and predicted together."""
+        from .gp import fit_folds, member_chunks
+
+        key, in_keys = self.output_key, self.inputs.get_keys()
+        pb = self._fit_problem(experiments[in_keys], experiments[[key]])
+        Xt, y, lo0, hi0 = pb["Xt"], pb["y"], pb["lo"], pb["hi"]
+        n, d = Xt.shape
+        B, nmax = len(splits), max(len(tr) for tr, _ in splits)
+        bounds = [self._bounds(experiments.iloc[tr][in_keys]) for tr, _ in splits]
+        Xb, Yb = np.zeros((B, nmax, d)), np.zeros((B, nmax))
+        for j, ((tr, _), (lo, hi)) in enumerate(zip(splits, bounds)):
+            Xb[j, :len(tr)] = (Xt[tr] - lo) / (hi - lo)
+            Yb[j, :len(tr)] = y[tr]
+        dev = device()
+        t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64), device=dev)  # noqa: E731
+        hyps = fit_folds(t(Xb), Yb, [len(tr) for tr, _ in splits], pb["kind"], pb["ls_prior"], pb["noise_prior"],
+                         pb["standardize"])
+        Xall, Xn_all = t(Xt), t((Xt - lo0) / (hi0 - lo0))
+        out = []
+        for ch in member_chunks(B, nmax, d):
+            mask = np.zeros((len(ch), n), dtype=bool)
+            folded = []
+            for k, j in enumerate(ch):
+                mask[k, splits[j][0]] = True
+                lo, hi = bounds[j]
+                h = hyps[j]
+                # the fold's Normalize bounds folded into its lengthscales: the stationary kernels
+                # see (x - x') / ((hi - lo) ls) only
+                folded.append(GPHyper(lengthscale=np.asarray(h.lengthscale) * ((hi - lo) / (hi0 - lo0)), noise=h.noise,
+                                      constant=h.constant, y_mean=h.y_mean, y_std=h.y_std))
+            gp = GPBatch(Xn_all, t(np.repeat(y[:, None], len(ch), 1)), folded, pb["kind"],
+                         t(lo0), t(hi0), mask=mask)
+            mean, var = gp.posterior(Xall, observation_noise=True)
+            mean, sd = mean.cpu().numpy(), np.sqrt(var.cpu().numpy())
+            for k, j in enumerate(ch):
+                tr, te = splits[j]
+                pred = {part: pd.DataFrame({f"{key}_pred": mean[k, rows], f"{key}_sd": sd[k, rows]},
+                                           index=experiments.index[rows])
+                        for part, rows in (("train", tr), ("test", te))}
+
+                def surrogate(j=j, tr=tr):
+                    sur = copy.copy(self)
+                    sur._set_state(Xt[tr], y[tr], *bounds[j], pb["kind"], hyps[j])
+                    return sur
+
+                out.append((surrogate, pred))
+        return out
 
     # ---- dump / load ------------------------------------------------------------------
     def dumps(self) -> str:

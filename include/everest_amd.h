@@ -111,6 +111,36 @@ int evr_mll_fit_rounds(void* stream, evr_mll_plan* plan, void** runs, int* task,
  * after the device work; evr_mll_fit_rounds applies the same code. */
 int evr_mll_assemble(int B, int n, int d, const double* prior, const double* x, const double* terms,
                      const double* gls, double* ll, double* g);
+/* ---- member form: B GPs on their own training rows (the folds of a cross-validation) -----
+ * Member b has its own normalised inputs Xb[b] (n x d, device; Xb is B x n x d) of which the
+ * first nvalid[b] <= n rows are real and the rest padding (finite values, zeros by
+ * convention).  Its train matrix is padded with the identity:
+ *   K[b][i][j] = k(|(x_bi - x_bj) / ls_b|) + diag_add[b] [i == j]      i, j < nvalid[b]
+ *              = [i == j] exactly                                       otherwise,
+ * so chol(K[b]) is the member's own factor with an identity block, and with r = 0 on the
+ * padded rows alpha is 0 there, W = alpha alpha^T - K^-1 is exactly 0 off the diagonal of the
+ * padded rows / columns, log det, r.alpha, sum alpha and sum alpha^2 are the member's own, and
+ * tr K^-1 is its own plus the pad count n - nvalid[b].  kind: one family 0..3; the dispatch
+ * (VALU differences for d < 16, MFMA distance expansion for 16 <= d <= 64) and the arithmetic
+ * of the valid block are evr_kernel_matrix's for the symmetric train matrix. */
+int evr_kernel_matrix_members(void* stream, int kind, int B, int n, int d, const double* Xb, const int* nvalid,
+                              const double* lengthscales, const double* diag_add, double* K);
+/* evr_kernel_lengthscale_grad with member b reading Xb[b] (same instantiations and summation
+ * order).  No nvalid: with the padding above W is exactly 0 off the diagonal of the padded rows
+ * and columns (a finite dK/dls times 0), and a diagonal entry has distance 0, i.e. dK/dls = 0. */
+int evr_kernel_lengthscale_grad_members(void* stream, int kind, int B, int n, int d, const double* Xb,
+                                        const double* lengthscales, const double* W, double* gls, double* work);
+/* evr_mll_plan_create for members: Xb (B x n x d, device, must outlive the plan), Y (B x n,
+ * device, copied; entries of padded rows ignored), nvalid (B, host, copied).  The plan is
+ * evaluated by evr_mll_plan_eval / evr_mll_fit_rounds as any other; r is 0 on padded rows, the
+ * reported tr K^-1 has the pad count subtracted, and evr_mll_fit_rounds scales member b by its
+ * own nvalid[b]: every reported term is the member's own GP's. */
+int evr_mll_plan_create_members(void* stream, int kind, int B, int n, int d, const double* Xb, const double* Y,
+                                const int* nvalid, evr_mll_plan** out);
+/* evr_mll_assemble with member b's own size nvalid[b] (host) for the -n/2 log 2 pi term and the
+ * 1 / n scaling. */
+int evr_mll_assemble_members(int B, const int* nvalid, int d, const double* prior, const double* x,
+                             const double* terms, const double* gls, double* ll, double* g);
 /* One member's L-BFGS-B after its evaluation at x (f, g): scipy's driver loop up to the next
  * evaluation request or the end (the state machine evr_mll_fit_rounds applies). */
 int evr_lbfgsb_advance(void* run, double f, const double* g, double* x, int* task, int* nit, int* nfev,
