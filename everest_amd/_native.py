@@ -224,6 +224,8 @@ _SIGS = {
     "evr_qreward_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
                           POINTER(EvrReward), c_int] + [c_void_p] * 5, c_int),
     "evr_nipv_reduce": ([c_void_p] + [c_int] * 7 + [c_void_p] * 2 + [c_int] + [c_void_p] * 13, c_int),
+    "evr_mixed_kernel_matrix": ([c_void_p] + [c_int] * 6 + [c_void_p] * 7, c_int),
+    "evr_mixed_kernel_param_grad": ([c_void_p] + [c_int] * 5 + [c_void_p] * 6, c_int),
     "evr_objective_general": ([c_void_p, c_int, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 4, c_int),
     "evr_objective_weights": ([c_void_p, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 3, c_int),
     "evr_cells_kd_limits": ([c_int, c_int, c_int, c_void_p], c_int),

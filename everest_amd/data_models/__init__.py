@@ -3,7 +3,8 @@ from .domain import (BaseModel, CategoricalInput, CloseToTargetObjective, Constr
                      LinearInequalityConstraint, MaximizeObjective, MaximizeSigmoidObjective, MinimizeObjective,
                      MinimizeSigmoidObjective, MovingMaximizeSigmoidObjective, Outputs, TargetObjective)
 from .models import (ActiveLearningStrategy, AdditiveSoboStrategy, AnyActiveLearningAcquisitionFunction, AnyStrategy, BotorchSurrogates, CategoricalEncodingEnum, CategoricalMethodEnum,
-                     DimensionalityScaledLogNormalPrior, GammaPrior, LogNormalPrior, MaternKernel, NormalPrior,
+                     DimensionalityScaledLogNormalPrior, GammaPrior, HammingDistanceKernel, LogNormalPrior, MaternKernel,
+                     MixedSingleTaskGPSurrogate, NormalPrior,
                      QehviStrategy, QnehviStrategy, QparegoStrategy, RandomStrategy, RBFKernel, ScalerEnum, SingleTaskGPSurrogate,
                      SoboStrategy, MoboStrategy, qEHVI, qEI, qLogEHVI, qLogEI, qLogNEHVI, qLogNEI, qNEHVI,
                      qNegIntPosVar, qNEI, qPI, qSR, qUCB)

@@ -117,6 +117,21 @@ class MaternKernel(BaseModel):
 AnyKernel = Annotated[Union[RBFKernel, MaternKernel], Field(discriminator="type")]
 
 
+class HammingDistanceKernel(BaseModel):
+    """bofire/data_models/kernels/categorical.py:10-12."""
+    type: Literal["HammingDistanceKernel"] = "HammingDistanceKernel"
+    features: Optional[List[str]] = None
+    ard: bool = True
+
+
+def THREESIX_LENGTHSCALE_PRIOR():  # bofire/data_models/priors/api.py:30-32
+    return GammaPrior(concentration=3.0, rate=6.0)
+
+
+def THREESIX_NOISE_PRIOR():
+    return GammaPrior(concentration=1.1, rate=0.05)
+
+
 # ---------------------------------------------------------------------------------------
 # surrogates
 # ---------------------------------------------------------------------------------------
@@ -150,6 +165,50 @@ class SingleTaskGPSurrogate(BaseModel):
         self.__dict__["input_preprocessing_specs"] = specs
         if len(self.outputs) != 1:
             raise ValueError("SingleTaskGPSurrogate takes exactly one output")
+        return self
+
+
+class MixedSingleTaskGPSurrogate(BaseModel):
+    """bofire/data_models/surrogates/mixed_single_task_gp.py:92-125 (without the hyperconfig): the
+    surrogate the reference builds per output for a domain with a CategoricalInput.  The
+    categorical kernel is always ARD over the categorical features on the device (the
+    reference's surrogate never passes ``categorical_kernel`` on to [upstream] MixedSingleTaskGP)."""
+    type: Literal["MixedSingleTaskGPSurrogate"] = "MixedSingleTaskGPSurrogate"
+    inputs: Inputs
+    outputs: Outputs
+    input_preprocessing_specs: Dict[str, CategoricalEncodingEnum] = Field(default_factory=dict, validate_default=True)
+    dump: Optional[str] = None
+    scaler: ScalerEnum = ScalerEnum.NORMALIZE
+    output_scaler: ScalerEnum = ScalerEnum.STANDARDIZE
+    continuous_kernel: AnyKernel = Field(default_factory=lambda: MaternKernel(
+        ard=True, nu=2.5, lengthscale_prior=THREESIX_LENGTHSCALE_PRIOR()))
+    categorical_kernel: HammingDistanceKernel = Field(default_factory=lambda: HammingDistanceKernel(ard=True))
+    noise_prior: AnyPrior = Field(default_factory=THREESIX_NOISE_PRIOR)
+
+    @field_validator("output_scaler")
+    @classmethod
+    def _os(cls, v):
+        if v == ScalerEnum.NORMALIZE:
+            raise ValueError("Normalize is not supported as an output transform.")
+        return v
+
+    @model_validator(mode="after")
+    def _specs(self):
+        """Categoricals are one-hot encoded (bofire/data_models/surrogates/botorch.py:19-60) and at
+        least one of them is present (mixed_single_task_gp.py:107-115); one continuous output."""
+        specs = dict(self.input_preprocessing_specs)
+        for key in self.inputs.get_keys(CategoricalInput):
+            if specs.get(key, CategoricalEncodingEnum.ONE_HOT) != CategoricalEncodingEnum.ONE_HOT:
+                raise ValueError("Botorch based models have to use one hot encodings for categoricals")
+            specs[key] = CategoricalEncodingEnum.ONE_HOT
+        if CategoricalEncodingEnum.ONE_HOT not in specs.values():
+            raise ValueError("MixedSingleTaskGPSurrogate can only be used if at least one one-hot encoded "
+                             "categorical feature is present.")
+        self.__dict__["input_preprocessing_specs"] = specs
+        if len(self.outputs) != 1:
+            raise ValueError("MixedSingleTaskGPSurrogate takes exactly one output")
+        if not isinstance(self.outputs.features[0], ContinuousOutput):
+            raise ValueError("MixedSingleTaskGPSurrogate takes a continuous output")
         return self
 
 

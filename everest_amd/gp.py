@@ -698,3 +698,222 @@ def fit_folds(Xb, Y_raw_b: np.ndarray, nvalid, kind: int, ls_prior, noise_prior,
         del ev          # the chunk's plan is freed before the next one is built
     LAST_FIT_STATS.update(driver=driver, nfev=nfev, nit=nit)
     return hypers
+
+
+# ---------------------------------------------------------------------------------------
+# mixed continuous / categorical GP ([upstream] BoTorch >= 0.13 MixedSingleTaskGP as built by
+# bofire/surrogates/mixed_single_task_gp.py:46-112)
+# ---------------------------------------------------------------------------------------
+# [upstream] restated (BoTorch is not installed; this is the specification the code follows):
+#   inputs    the transformed row is split into Xc (n x dc, continuous columns, Normalize bounds)
+#             and C (n x nc int32 category codes, OneHotToNumeric: arg-max of each one-hot block)
+#   kernel    K(x, x') = s_sum (k_c(r1) + s_cat h1) + s_prod k_c(r2) h2 — ScaleKernel(k_c + ScaleKernel(
+#             CategoricalKernel)) + ScaleKernel(k_c * CategoricalKernel), the kernel factories
+#             called twice, so two independent continuous and two independent categorical kernels;
+#             r_t^2 = sum_k ((xc_k - xc'_k) / ls_t,k)^2, h_t = exp(-(1 / nc) sum_f [c_f != c'_f] / lam_t,f)
+#   raw       ls = softplus(raw), lam = 1e-6 + softplus(raw) (GreaterThan(1e-6)), outputscales =
+#             softplus(raw), all raw 0 at the start; noise a direct parameter >= 1e-6 starting at
+#             1e-3; constant mean a direct parameter starting at 0
+#   priors    the data model's lengthscale prior on ls1 and on ls2, its noise prior on the noise;
+#             none on lam and the outputscales
+#   loss      (MLL + sum log prior) / n on standardised targets, as MLLEvaluator
+#   fit       scipy L-BFGS-B; on NotPSDError the parameters with priors are resampled, 5 attempts
+#             (fit_gpytorch_mll's default: the reference passes no max_attempts here)
+MIXED_MIN_NOISE = 1e-6
+MIXED_MIN_LAM = 1e-6
+MIXED_NOISE0 = 1e-3
+
+
+@dataclass
+class MixedGPHyper:
+    params: np.ndarray        # P = 2 dc + 2 nc + 3: [ls1 | ls2 | lam1 | lam2 | s_sum | s_cat | s_prod]
+    noise: float
+    constant: float
+    y_mean: float
+    y_std: float
+
+
+def mixed_kxx(params: np.ndarray) -> float:
+    """k(x, x) = s_sum (1 + s_cat) + s_prod."""
+    s_sum, s_cat, s_prod = np.asarray(params, dtype=np.float64)[-3:]
+    return float(s_sum * (1.0 + s_cat) + s_prod)
+
+
+class MixedMLLEvaluator:
+    """Exact MLL / n with hyperpriors of the mixed GP on the device, the op-by-op chain of
+    MLLEvaluator with the mixed kernel.  Raw parameter vector
+    x = [noise, constant, raw ls1, raw ls2, raw lam1 (nc), raw lam2 (nc), raw s_sum, raw s_cat,
+    raw s_prod]; raw ls1 / ls2 hold dc values each, or one each with ``ard=False`` (the shared
+    lengthscale is broadcast and its gradient summed here)."""
+
+    def __init__(self, Xc: torch.Tensor, C: torch.Tensor, y_std_space: np.ndarray, kind: int, ls_prior,
+                 noise_prior, ard: bool = True):
+        self.Xc = Xc.contiguous()
+        self.C = C.contiguous()
+        self.n, self.dc = Xc.shape
+        self.nc = C.shape[1]
+        self.kind = int(kind)
+        self.ard = bool(ard)
+        self.nls = self.dc if self.ard else 1
+        self.y = np.asarray(y_std_space, dtype=np.float64)
+        self.ls_prior = _prior(ls_prior)
+        self.noise_prior = _prior(noise_prior)
+        self.dev = Xc.device
+
+    @property
+    def nx(self) -> int:
+        return 2 + 2 * self.nls + 2 * self.nc + 3
+
+    def start(self) -> np.ndarray:
+        x0 = np.zeros(self.nx)
+        x0[0] = MIXED_NOISE0
+        return x0
+
+    def bounds(self):
+        return [(MIXED_MIN_NOISE, None)] + [(None, None)] * (self.nx - 1)
+
+    def split(self, x):
+        """(noise, constant, raw kernel part in the device layout's order) of x."""
+        x = np.asarray(x, dtype=np.float64)
+        return float(x[0]), float(x[1]), x[2:]
+
+    def params_of(self, x) -> np.ndarray:
+        """The device parameter vector (P) of x."""
+        _, _, raw = self.split(x)
+        nls, nc, dc = self.nls, self.nc, self.dc
+        ls = softplus_np(raw[:2 * nls]).reshape(2, nls)
+        lam = MIXED_MIN_LAM + softplus_np(raw[2 * nls:2 * nls + 2 * nc])
+        s = softplus_np(raw[2 * nls + 2 * nc:])
+        return np.concatenate([np.broadcast_to(ls[:, :1] if not self.ard else ls, (2, dc)).reshape(-1), lam, s])
+
+    def x_of(self, params, noise: float, constant: float) -> np.ndarray:
+        """Raw vector of given parameter values (ard=False: the first lengthscale of each kernel)."""
+        params = np.asarray(params, dtype=np.float64)
+        dc, nc = self.dc, self.nc
+        ls = params[:2 * dc].reshape(2, dc)[:, :self.nls].reshape(-1)
+        lam = params[2 * dc:2 * dc + 2 * nc] - MIXED_MIN_LAM
+        inv = lambda v: v + np.log(-np.expm1(-v))   # noqa: E731
+        return np.concatenate([[noise, constant], inv(ls), inv(lam), inv(params[-3:])])
+
+    def hyper(self, x, y_mean: float, y_std: float) -> MixedGPHyper:
+        noise, const, _ = self.split(x)
+        return MixedGPHyper(params=self.params_of(x), noise=noise, constant=const, y_mean=y_mean, y_std=y_std)
+
+    def __call__(self, x: np.ndarray):
+        n, dc = self.n, self.dc
+        noise, const, raw = self.split(x)
+        params = self.params_of(x)
+        dev = self.dev
+        p_t = torch.as_tensor(params[None, :], device=dev)
+        Ky = ops.mixed_kernel_matrix(self.Xc, self.C, self.Xc, self.C, p_t, self.kind,
+                                     diag_add=torch.tensor([noise], dtype=torch.float64, device=dev))
+        L, Linv, _, _ = ops.cholesky_inverse(Ky, 1e-8, 3)
+        r = torch.as_tensor((self.y - const)[None, :, None], device=dev)
+        v = ops.gemm(Linv, r)
+        alpha = ops.gemm(Linv, v, transA=True)                       # 1 x n x 1
+        W = ops.gemm(alpha, alpha, transB=True)                      # alpha alpha^T
+        ops.gemm(Linv, Linv, transA=True, alpha=-1.0, beta=1.0, out=W)   # - K^-1
+        gk = ops.mixed_kernel_param_grad(self.Xc, self.C, p_t, W, self.kind)  # 1 x P
+        terms = ops.mll_terms(L, Linv, r[..., 0].contiguous(), alpha[..., 0].contiguous())
+        terms = terms.cpu().numpy()[0]
+        gk = 0.5 * gk.cpu().numpy()[0]
+        logdet, quad, trKinv, sum_a, sum_a2 = terms
+        ll = -0.5 * quad - 0.5 * logdet - 0.5 * n * math.log(2 * math.pi)
+        d_noise = 0.5 * (sum_a2 - trKinv)
+        d_const = sum_a
+        # the lengthscales as the optimiser sees them (2 x nls): ard=False sums the dc gradients
+        d_ls = gk[:2 * dc].reshape(2, dc)
+        ls = params[:2 * dc].reshape(2, dc)
+        if not self.ard:
+            d_ls, ls = d_ls.sum(1, keepdims=True), ls[:, :1]
+        if self.ls_prior is not None:
+            ll += float(np.sum(prior_logpdf_np(self.ls_prior, ls)))
+            d_ls = d_ls + prior_dlogpdf_np(self.ls_prior, ls)
+        if self.noise_prior is not None:
+            ll += float(prior_logpdf_np(self.noise_prior, noise))
+            d_noise += float(prior_dlogpdf_np(self.noise_prior, noise))
+        d_val = np.concatenate([d_ls.reshape(-1), gk[2 * dc:]])      # d / d(ls, lam, scales)
+        with np.errstate(over="ignore"):     # exp(-raw) = inf at a very negative raw: sigmoid 0, as it should be
+            g = np.concatenate([[d_noise, d_const], d_val * sigmoid_np(raw)]) / n
+        return ll / n, g
+
+
+def fit_mixed(Xc: torch.Tensor, C: torch.Tensor, y_raw: np.ndarray, kind: int, ls_prior, noise_prior,
+              ard: bool = True, max_attempts: int = 5, seed: int = 0, options: Optional[dict] = None,
+              standardize: bool = True) -> MixedGPHyper:
+    """fit_gpytorch_mll of the mixed GP restated on the device kernels: scipy L-BFGS-B on -MLL / n
+    over the raw parameters of MixedMLLEvaluator (noise >= 1e-6), from noise 1e-3, constant 0 and
+    every raw kernel parameter 0; on NotPSDError the parameters with priors (both lengthscale
+    sets, the noise) are resampled from them, the others go back to the start, and the fit is
+    retried (max_attempts = 5, fit_gpytorch_mll's default)."""
+    from scipy.optimize import minimize
+
+    y_raw = np.asarray(y_raw, dtype=np.float64)
+    y_mean, y_std = standardize_params(y_raw) if standardize else (0.0, 1.0)
+    ev = MixedMLLEvaluator(Xc, C, (y_raw - y_mean) / y_std, kind, ls_prior, noise_prior, ard=ard)
+    x0 = ev.start()
+    rng = np.random.default_rng(seed)
+    last_err = None
+    for _ in range(max_attempts):
+        try:
+            res = minimize(lambda x: tuple(-v for v in ev(x)), x0, jac=True, method="L-BFGS-B", bounds=ev.bounds(),
+                           options=options or {})
+            return ev.hyper(res.x, y_mean, y_std)
+        except ops.NotPSDError as e:  # sample_all_priors, then retry
+            last_err = e
+            x0 = ev.start()
+            if ev.ls_prior is not None:
+                ls = prior_sample_np(ev.ls_prior, rng, 2 * ev.nls)
+                x0[2:2 + 2 * ev.nls] = np.log(np.expm1(ls))
+            if ev.noise_prior is not None:
+                x0[0] = max(float(prior_sample_np(ev.noise_prior, rng, 1)[0]), MIXED_MIN_NOISE)
+    raise RuntimeError(f"mixed GP fit failed after {max_attempts} attempts: {last_err}")
+
+
+class MixedGPBatch:
+    """B mixed GPs (B = 1 is what the surrogate builds) on shared training inputs: Xc (n x dc,
+    normalised continuous columns, device) and C (n x nc int32 category codes, device).  Test
+    inputs are given the same way (the caller normalises and encodes)."""
+
+    def __init__(self, Xc: torch.Tensor, C: torch.Tensor, Y: torch.Tensor, hypers: Sequence[MixedGPHyper], kind: int):
+        self.Xc = Xc.contiguous()
+        self.C = C.to(torch.int32).contiguous()
+        self.kind = int(kind)
+        self.hypers = list(hypers)
+        dev = Xc.device
+        self.device = dev
+        self.B = len(self.hypers)
+        self.n, self.dc = Xc.shape
+        self.nc = self.C.shape[1]
+        t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64), device=dev)  # noqa: E731
+        self.params = t(np.stack([h.params for h in self.hypers]))
+        self.noise = t([h.noise for h in self.hypers])
+        self.const = t([h.constant for h in self.hypers])
+        self.ym = t([h.y_mean for h in self.hypers])
+        self.ys = t([h.y_std for h in self.hypers])
+        self.kxx = t([mixed_kxx(h.params) for h in self.hypers])
+        Yc = Y.to(device=dev, dtype=torch.float64).reshape(self.n, self.B).T.contiguous()
+        self.y = ((Yc - self.ym[:, None]) / self.ys[:, None]).contiguous()
+        self.refresh()
+
+    # -- caches: L = chol(K + s2 I), Linv, alpha, M = [Linv; alpha^T] ----------------------
+    def refresh(self):
+        Ky = ops.mixed_kernel_matrix(self.Xc, self.C, self.Xc, self.C, self.params, self.kind, diag_add=self.noise)
+        self.L, self.Linv, _, _ = ops.cholesky_inverse(Ky, 1e-8, 3)
+        r = (self.y - self.const[:, None]).unsqueeze(-1).contiguous()           # B x n x 1
+        v = ops.gemm(self.Linv, r)
+        self.alpha = ops.gemm(self.Linv, v, transA=True)[..., 0].contiguous()  # B x n
+        self.M = torch.cat([self.Linv, self.alpha.unsqueeze(1)], dim=1).contiguous()  # B x (n+1) x n
+
+    def cross(self, Xc: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+        """K(train, test): B x n x nt."""
+        return ops.mixed_kernel_matrix(self.Xc, self.C, Xc, C, self.params, self.kind)
+
+    def posterior(self, Xc: torch.Tensor, C: torch.Tensor, observation_noise: bool = False):
+        """Mean and variance (B x nt) at normalised continuous columns Xc and category codes C:
+        K_* = cross, R = M K_*, then the posterior finalize with k(x, x) = s_sum (1 + s_cat) + s_prod."""
+        Xc = Xc.to(device=self.device, dtype=torch.float64).contiguous()
+        C = C.to(device=self.device, dtype=torch.int32).contiguous()
+        R = ops.gemm(self.M, self.cross(Xc, C))
+        return ops.posterior_finalize(R, self.const, self.ym, self.ys, self.kxx,
+                                      self.noise if observation_noise else None)

@@ -144,6 +144,70 @@ def kernel_lengthscale_grad_members(Xb, lengthscales, W, kind=0) -> torch.Tensor
     return g
 
 
+# limits of the mixed-kernel entry points (include/everest_amd.h)
+MIXED_MAX_DC, MIXED_MAX_NC = 32, 8
+
+
+def _mixed_args(Xc, C, params, name: str):
+    Xc, C, params = _dev(Xc, f"{name}: Xc"), _dev(C, f"{name}: C", torch.int32), _dev(params, f"{name}: params")
+    if params.dim() == 1:
+        params = params.unsqueeze(0)
+    if Xc.dim() != 2 or C.dim() != 2 or C.shape[0] != Xc.shape[0] or params.dim() != 2:
+        raise ValueError(f"{name}: Xc {tuple(Xc.shape)} must be n x dc, C {tuple(C.shape)} n x nc, params B x P")
+    dc, nc = Xc.shape[1], C.shape[1]
+    if params.shape[1] != 2 * dc + 2 * nc + 3:
+        raise ValueError(f"{name}: params {tuple(params.shape)} must hold 2 dc + 2 nc + 3 = {2 * dc + 2 * nc + 3} "
+                         "values per member")
+    return Xc, C, params, dc, nc
+
+
+def _mixed_call(symbol: str, dc: int, nc: int, *args):
+    """The native call; sizes the kernels are not built for (the library's own error, never a
+    silent fall-through) surface as NotImplementedError."""
+    try:
+        call(symbol, *args)
+    except RuntimeError as e:
+        if not (1 <= dc <= MIXED_MAX_DC and 1 <= nc <= MIXED_MAX_NC):
+            raise NotImplementedError(str(e)) from e
+        raise
+
+
+def mixed_kernel_matrix(X1c, C1, X2c, C2, params, kind: int = 3, diag_add=None) -> torch.Tensor:
+    """K[b] (B x n1 x n2) of the mixed kernel (evr_mixed_kernel_matrix):
+    s_sum (k_c(r1) + s_cat h1) + s_prod k_c(r2) h2 (+ diag_add_b on i == j).  X?c: n? x dc normalised
+    continuous columns, C?: n? x nc int32 category codes, params: B x (2 dc + 2 nc + 3) =
+    [ls1 | ls2 | lam1 | lam2 | s_sum | s_cat | s_prod].  1 <= dc <= 32, 1 <= nc <= 8."""
+    X1c, C1, params, dc, nc = _mixed_args(X1c, C1, params, "mixed_kernel_matrix")
+    X2c, C2 = _dev(X2c, "mixed_kernel_matrix: X2c"), _dev(C2, "mixed_kernel_matrix: C2", torch.int32)
+    if X2c.dim() != 2 or C2.dim() != 2 or X2c.shape[1] != dc or C2.shape[1] != nc or C2.shape[0] != X2c.shape[0]:
+        raise ValueError(f"mixed_kernel_matrix: X2c {tuple(X2c.shape)} / C2 {tuple(C2.shape)} do not match "
+                         f"dc = {dc}, nc = {nc}")
+    B, n1, n2 = params.shape[0], X1c.shape[0], X2c.shape[0]
+    K = torch.empty(B, n1, n2, dtype=torch.float64, device=X1c.device)
+    dg = None if diag_add is None else _dev(diag_add, "diag_add")
+    if dg is not None and dg.numel() != B:
+        raise ValueError(f"mixed_kernel_matrix: diag_add holds {dg.numel()} values for {B} members")
+    _mixed_call("evr_mixed_kernel_matrix", dc, nc, _stream(), int(kind), B, n1, n2, dc, nc, X1c.data_ptr(),
+                C1.data_ptr(), X2c.data_ptr(), C2.data_ptr(), params.data_ptr(), _p(dg), K.data_ptr())
+    return K
+
+
+def mixed_kernel_param_grad(Xc, C, params, W, kind: int = 3) -> torch.Tensor:
+    """g[b][p] = sum_ij W[b][i][j] dK_b[i][j] / dparams_p (B x P) in one pass over W (B x n x n, need
+    not be symmetric); evr_mixed_kernel_param_grad.  Bitwise reproducible."""
+    Xc, C, params, dc, nc = _mixed_args(Xc, C, params, "mixed_kernel_param_grad")
+    W = _dev(W, "W")
+    B, P = params.shape
+    n = Xc.shape[0]
+    if tuple(W.shape) != (B, n, n):
+        raise ValueError(f"mixed_kernel_param_grad: W shape {tuple(W.shape)} != {(B, n, n)}")
+    g = torch.empty(B, P, dtype=torch.float64, device=Xc.device)
+    work = torch.empty(B, n, P, dtype=torch.float64, device=Xc.device)
+    _mixed_call("evr_mixed_kernel_param_grad", dc, nc, _stream(), int(kind), B, n, dc, nc, Xc.data_ptr(),
+                C.data_ptr(), params.data_ptr(), W.data_ptr(), g.data_ptr(), work.data_ptr())
+    return g
+
+
 def mll_terms(L, Linv, r, alpha) -> torch.Tensor:
     """B x 5: logdet, quad, tr(K^-1), sum(alpha), sum(alpha^2)."""
     L, Linv, r, alpha = _dev(L, "L"), _dev(Linv, "Linv"), _dev(r, "r"), _dev(alpha, "alpha")

@@ -1,5 +1,6 @@
 """Functional surrogates on the device — mirrors bofire/surrogates/{single_task_gp,botorch,
-surrogate,trainable,botorch_surrogates}.py for ``SingleTaskGPSurrogate``.
+surrogate,trainable,botorch_surrogates}.py for ``SingleTaskGPSurrogate``, and
+bofire/surrogates/mixed_single_task_gp.py for ``MixedSingleTaskGPSurrogate``.
 
 The fitted model (transformed training inputs, targets, hyperparameters, Normalize bounds,
 kernel family) is the wire format of ``dumps()/loads()`` — a versioned JSON + base64(npz)
@@ -113,6 +114,69 @@ def map_prior(prior, d: int) -> Optional[Tuple[str, float, float]]:
     if isinstance(prior, NormalPrior):
         return ("normal", float(prior.loc), float(prior.scale))
     raise NotImplementedError(type(prior).__name__)
+
+
+def run_cross_validation(surrogate_, fit_folds: Callable, experiments: pd.DataFrame, folds: int = -1,
+                         include_X: bool = False, include_labcodes: bool = False,
+                         random_state: Optional[int] = None, stratified_feature: Optional[str] = None,
+                         group_split_column: Optional[str] = None, hooks: Optional[Dict[str, Callable]] = None,
+                         hook_kwargs: Optional[Dict[str, Dict[str, Any]]] = None
+                         ) -> Tuple[CvResults, CvResults, Dict[str, list]]:
+    """The argument checks, split, result and hook code of ``cross_validate``
+    (bofire/surrogates/trainable.py:79-339), shared by the surrogate classes.
+    ``fit_folds(experiments, splits)`` returns, per fold, (surrogate getter, {"train" / "test":
+    predictions}) on the rows valid for the surrogate's output."""
+    if include_labcodes and "labcode" not in experiments.columns:
+        raise ValueError("No labcodes available for the provided experiments.")
+    if len(surrogate_.outputs) > 1:
+        raise NotImplementedError("Cross validation not implemented for multi-output models")
+    if stratified_feature is not None:
+        if stratified_feature not in surrogate_.inputs.get_keys() + surrogate_.outputs.get_keys():
+            raise ValueError("The feature to be stratified is not in the model inputs or outputs")
+        feats = surrogate_.inputs if stratified_feature in surrogate_.inputs.get_keys() else surrogate_.outputs
+        if not isinstance(feats.get_by_key(stratified_feature), _STRATIFIABLE):
+            raise ValueError("The feature to be stratified needs to be a DiscreteInput, CategoricalInput, "
+                             "CategoricalOutput, or ContinuousOutput")
+    if group_split_column is not None:
+        if group_split_column not in experiments.columns:
+            raise ValueError(f"Group split column {group_split_column} is not present in the experiments.")
+        ngroups = experiments[group_split_column].nunique(dropna=False)
+        if ngroups < folds:
+            raise ValueError(f"Number of unique groups {ngroups} is less than the number of folds {folds}.")
+    experiments = surrogate_._preprocess_experiments(experiments)
+    folds = check_valid_nfolds(folds, len(experiments))
+    splits = cv_splits(experiments, folds, random_state, stratified_feature, group_split_column)
+    hooks, hook_kwargs = hooks or {}, hook_kwargs or {}
+    key, in_keys = surrogate_.output_key, surrogate_.inputs.get_keys()
+    fitted = fit_folds(experiments, splits)
+    train_results, test_results, hook_results = [], [], {name: [] for name in hooks}
+    for (tr, te), (surrogate, pred) in zip(splits, fitted):
+        rows = {"train": experiments.iloc[tr], "test": experiments.iloc[te]}
+        for part, out in (("train", train_results), ("test", test_results)):
+            df = rows[part]
+            out.append(CvResult(key=key, observed=df[key], predicted=pred[part][f"{key}_pred"],
+                                standard_deviation=pred[part][f"{key}_sd"],
+                                X=df[in_keys] if include_X else None,
+                                labcodes=df["labcode"] if include_labcodes else None))
+        fold_model = surrogate() if hooks else None      # built only when a hook asks for it
+        for name, hook in hooks.items():
+            hook_results[name].append(hook(surrogate=fold_model, X_train=rows["train"][in_keys],
+                                           y_train=rows["train"][[key]], X_test=rows["test"][in_keys],
+                                           y_test=rows["test"][[key]], **hook_kwargs.get(name, {})))
+    return CvResults(train_results), CvResults(test_results), hook_results
+
+
+def cv_sequential(surrogate_, experiments: pd.DataFrame, splits):
+    """Per fold (surrogate getter, {"train" / "test": predictions}): one fit after another, a
+    fresh copy of the surrogate per fold."""
+    key, in_keys = surrogate_.output_key, surrogate_.inputs.get_keys()
+    out = []
+    for tr, te in splits:
+        sur = copy.copy(surrogate_)
+        sur._fit(experiments.iloc[tr][in_keys], experiments.iloc[tr][[key]])
+        out.append((lambda s=sur: s, {"train": sur.predict(experiments.iloc[tr][in_keys]),
+                                      "test": sur.predict(experiments.iloc[te][in_keys])}))
+    return out
 
 
 class SingleTaskGPSurrogate:
@@ -250,56 +314,14 @@ class SingleTaskGPSurrogate:
         fitted state is left as it was.  Plain K-fold splits are those of
         ``sklearn.model_selection.KFold(shuffle=True, random_state=random_state)`` (kfold_indices);
         ``stratified_feature`` and ``group_split_column`` need scikit-learn."""
-        if include_labcodes and "labcode" not in experiments.columns:
-            raise ValueError("No labcodes available for the provided experiments.")
-        if len(self.outputs) > 1:
-            raise NotImplementedError("Cross validation not implemented for multi-output models")
-        if stratified_feature is not None:
-            if stratified_feature not in self.inputs.get_keys() + self.outputs.get_keys():
-                raise ValueError("The feature to be stratified is not in the model inputs or outputs")
-            feats = self.inputs if stratified_feature in self.inputs.get_keys() else self.outputs
-            if not isinstance(feats.get_by_key(stratified_feature), _STRATIFIABLE):
-                raise ValueError("The feature to be stratified needs to be a DiscreteInput, CategoricalInput, "
-                                 "CategoricalOutput, or ContinuousOutput")
-        if group_split_column is not None:
-            if group_split_column not in experiments.columns:
-                raise ValueError(f"Group split column {group_split_column} is not present in the experiments.")
-            ngroups = experiments[group_split_column].nunique(dropna=False)
-            if ngroups < folds:
-                raise ValueError(f"Number of unique groups {ngroups} is less than the number of folds {folds}.")
-        experiments = self._preprocess_experiments(experiments)
-        folds = check_valid_nfolds(folds, len(experiments))
-        splits = cv_splits(experiments, folds, random_state, stratified_feature, group_split_column)
-        hooks, hook_kwargs = hooks or {}, hook_kwargs or {}
-        key, in_keys = self.output_key, self.inputs.get_keys()
         lockstep = os.environ.get("EVR_CV_LOCKSTEP", "1") != "0"
-        fitted = self._cv_lockstep(experiments, splits) if lockstep else self._cv_sequential(experiments, splits)
-        train_results, test_results, hook_results = [], [], {name: [] for name in hooks}
-        for (tr, te), (surrogate, pred) in zip(splits, fitted):
-            rows = {"train": experiments.iloc[tr], "test": experiments.iloc[te]}
-            for part, out in (("train", train_results), ("test", test_results)):
-                df = rows[part]
-                out.append(CvResult(key=key, observed=df[key], predicted=pred[part][f"{key}_pred"],
-                                    standard_deviation=pred[part][f"{key}_sd"],
-                                    X=df[in_keys] if include_X else None,
-                                    labcodes=df["labcode"] if include_labcodes else None))
-            fold_model = surrogate() if hooks else None      # built only when a hook asks for it
-            for name, hook in hooks.items():
-                hook_results[name].append(hook(surrogate=fold_model, X_train=rows["train"][in_keys],
-                                               y_train=rows["train"][[key]], X_test=rows["test"][in_keys],
-                                               y_test=rows["test"][[key]], **hook_kwargs.get(name, {})))
-        return CvResults(train_results), CvResults(test_results), hook_results
+        return run_cross_validation(self, self._cv_lockstep if lockstep else self._cv_sequential, experiments,
+                                    folds, include_X, include_labcodes, random_state, stratified_feature,
+                                    group_split_column, hooks, hook_kwargs)
 
     def _cv_sequential(self, experiments: pd.DataFrame, splits):
         """Per fold (surrogate getter, {"train" / "test": predictions}): one fit after another."""
-        key, in_keys = self.output_key, self.inputs.get_keys()
-        out = []
-        for tr, te in splits:
-            sur = copy.copy(self)
-            sur._fit(experiments.iloc[tr][in_keys], experiments.iloc[tr][[key]])
-            out.append((lambda s=sur: s, {"train": sur.predict(experiments.iloc[tr][in_keys]),
-                                          "test": sur.predict(experiments.iloc[te][in_keys])}))
-        return out
+        return cv_sequential(self, experiments, splits)
 
     def _cv_lockstep(self, experiments: pd.DataFrame, splits):
         """_cv_sequential's result with all folds fitted in lock-step and predicted together."""
@@ -369,6 +391,159 @@ class SingleTaskGPSurrogate:
         arr = np.load(io.BytesIO(base64.b64decode(meta["arrays"])), allow_pickle=False)
         hyp = GPHyper(lengthscale=arr["lengthscale"], noise=meta["noise"], constant=meta["constant"],
                       y_mean=meta["y_mean"], y_std=meta["y_std"])
+        self._set_state(arr["X"], arr["y"], arr["lo"], arr["hi"], meta["kind"], hyp)
+
+
+class MixedSingleTaskGPSurrogate:
+    """Mixed continuous / categorical exact GP for one output
+    (bofire/surrogates/mixed_single_task_gp.py:27-112 on [upstream] BoTorch MixedSingleTaskGP;
+    the model is restated in gp.py).  The transformed (one-hot) row is split on the host into the
+    continuous columns, normalised with the bounds of get_scaler as SingleTaskGPSurrogate does,
+    and one category code per categorical feature: the arg-max of its one-hot block, the first
+    on ties ([upstream] OneHotToNumeric).  Needs at least one continuous and one categorical
+    input; up to 32 continuous columns and 8 categorical features."""
+
+    FORMAT = "everest_amd.MixedSingleTaskGP/1"
+
+    def __init__(self, data_model: dm.MixedSingleTaskGPSurrogate):
+        self.data_model = data_model
+        self.inputs = data_model.inputs
+        self.outputs = data_model.outputs
+        self.continuous_kernel = data_model.continuous_kernel
+        self.categorical_kernel = data_model.categorical_kernel
+        self.noise_prior = data_model.noise_prior
+        self.scaler = data_model.scaler
+        self.output_scaler = data_model.output_scaler
+        self.input_preprocessing_specs = {k: v.value if hasattr(v, "value") else v
+                                          for k, v in data_model.input_preprocessing_specs.items()}
+        f2i, _ = self.inputs._transform_info(self.input_preprocessing_specs)
+        cat_keys = [k for k in self.inputs.get_keys(dm.CategoricalInput)
+                    if self.input_preprocessing_specs.get(k) == CategoricalEncodingEnum.ONE_HOT.value]
+        self._cat_blocks = [np.asarray(f2i[k]) for k in cat_keys]
+        self._cont_cols = np.asarray([j for k in self.inputs.get_keys() if k not in cat_keys for j in f2i[k]],
+                                     dtype=np.int64)
+        if len(self._cont_cols) < 1 or len(self._cat_blocks) < 1:
+            raise ValueError("MixedSingleTaskGPSurrogate needs at least one continuous and one categorical input")
+        self.state: Optional[dict] = None
+        self.gp = None
+        if data_model.dump is not None:
+            self.loads(data_model.dump)
+
+    @property
+    def is_fitted(self) -> bool:
+        return self.state is not None
+
+    @property
+    def output_key(self) -> str:
+        return self.outputs.get_keys()[0]
+
+    # ---- transforms ----------------------------------------------------------------
+    _bounds = SingleTaskGPSurrogate._bounds
+    transform_inputs = SingleTaskGPSurrogate.transform_inputs
+    _preprocess_experiments = SingleTaskGPSurrogate._preprocess_experiments
+    _fit_data = SingleTaskGPSurrogate._fit_data
+
+    def split_inputs(self, Xt: np.ndarray, lo: np.ndarray, hi: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(Xc, C) of transformed rows: the normalised continuous columns (n x dc) and the int32
+        category codes (n x nc).  lo / hi: the Normalize bounds of all transformed columns."""
+        cc = self._cont_cols
+        Xc = (Xt[:, cc] - lo[cc]) / (hi[cc] - lo[cc])
+        C = np.stack([np.argmax(Xt[:, blk], axis=1) for blk in self._cat_blocks], axis=1).astype(np.int32)
+        return np.ascontiguousarray(Xc), np.ascontiguousarray(C)
+
+    # ---- fit -------------------------------------------------------------------------
+    def fit(self, experiments: pd.DataFrame, options: Optional[dict] = None):
+        """TrainableSurrogate.fit (bofire/surrogates/trainable.py:24-42): valid rows of this output."""
+        X, Y = self._fit_data(experiments)
+        self._fit(X, Y, options)
+
+    def _fit(self, X: pd.DataFrame, Y: pd.DataFrame, options: Optional[dict] = None):
+        from .gp import fit_mixed
+
+        Xt = self.transform_inputs(X)
+        lo, hi = self._bounds(X)
+        y = Y.values[:, 0].astype(np.float64)
+        Xc, C = self.split_inputs(Xt, lo, hi)
+        dev = device()
+        kernel = self.continuous_kernel
+        kind = kernel_kind(kernel)
+        hyp = fit_mixed(torch.as_tensor(Xc, device=dev), torch.as_tensor(C, device=dev), y, kind,
+                        map_prior(getattr(kernel, "lengthscale_prior", None), Xc.shape[1]),
+                        map_prior(self.noise_prior, 1), ard=kernel.ard, options=options,
+                        standardize=self.output_scaler == ScalerEnum.STANDARDIZE)
+        self._set_state(Xt, y, lo, hi, kind, hyp)
+
+    def _set_state(self, Xt, y, lo, hi, kind, hyp):
+        self.state = dict(X=np.asarray(Xt), y=np.asarray(y), lo=np.asarray(lo), hi=np.asarray(hi), kind=int(kind),
+                          params=np.asarray(hyp.params, dtype=np.float64), noise=float(hyp.noise),
+                          constant=float(hyp.constant), y_mean=float(hyp.y_mean), y_std=float(hyp.y_std))
+        self.gp = self._build_gp()
+
+    def hyper(self):
+        from .gp import MixedGPHyper
+
+        s = self.state
+        return MixedGPHyper(params=s["params"], noise=s["noise"], constant=s["constant"], y_mean=s["y_mean"],
+                            y_std=s["y_std"])
+
+    def _build_gp(self):
+        from .gp import MixedGPBatch
+
+        s = self.state
+        dev = device()
+        Xc, C = self.split_inputs(s["X"], s["lo"], s["hi"])
+        return MixedGPBatch(torch.as_tensor(Xc, device=dev), torch.as_tensor(C, device=dev),
+                            torch.as_tensor(s["y"][:, None], dtype=torch.float64, device=dev), [self.hyper()],
+                            s["kind"])
+
+    # ---- predict ----------------------------------------------------------------------
+    def predict(self, experiments: pd.DataFrame) -> pd.DataFrame:
+        """Surrogate.predict (bofire/surrogates/surrogate.py:39-67): posterior(observation_noise=True)."""
+        if not self.is_fitted:
+            raise ValueError("Model is not fitted/available yet.")
+        Xt = self.transform_inputs(experiments[self.inputs.get_keys()])
+        Xc, C = self.split_inputs(Xt, self.state["lo"], self.state["hi"])
+        dev = self.gp.device
+        mean, var = self.gp.posterior(torch.as_tensor(Xc, device=dev), torch.as_tensor(C, device=dev),
+                                      observation_noise=True)
+        key = self.output_key
+        return pd.DataFrame({f"{key}_pred": mean[0].cpu().numpy(), f"{key}_sd": np.sqrt(var[0].cpu().numpy())},
+                            index=experiments.index)
+
+    # ---- cross-validation --------------------------------------------------------------
+    def cross_validate(self, experiments: pd.DataFrame, folds: int = -1, include_X: bool = False,
+                       include_labcodes: bool = False, random_state: Optional[int] = None,
+                       stratified_feature: Optional[str] = None, group_split_column: Optional[str] = None,
+                       hooks: Optional[Dict[str, Callable]] = None,
+                       hook_kwargs: Optional[Dict[str, Dict[str, Any]]] = None
+                       ) -> Tuple[CvResults, CvResults, Dict[str, list]]:
+        """TrainableSurrogate.cross_validate (bofire/surrogates/trainable.py:79-339), arguments and
+        return value as SingleTaskGPSurrogate.cross_validate: the plain sequential loop, a fresh
+        surrogate per fold.  This surrogate's own fitted state is left as it was."""
+        return run_cross_validation(self, lambda ex, splits: cv_sequential(self, ex, splits), experiments, folds,
+                                    include_X, include_labcodes, random_state, stratified_feature,
+                                    group_split_column, hooks, hook_kwargs)
+
+    # ---- dump / load ------------------------------------------------------------------
+    def dumps(self) -> str:
+        if not self.is_fitted:
+            raise ValueError("Model is not fitted/available yet.")
+        buf = io.BytesIO()
+        s = self.state
+        np.savez(buf, X=s["X"], y=s["y"], lo=s["lo"], hi=s["hi"], params=s["params"])
+        meta = {"format": self.FORMAT, "kind": s["kind"], "noise": s["noise"], "constant": s["constant"],
+                "y_mean": s["y_mean"], "y_std": s["y_std"], "arrays": base64.b64encode(buf.getvalue()).decode()}
+        return base64.b64encode(json.dumps(meta).encode()).decode()
+
+    def loads(self, data: str):
+        from .gp import MixedGPHyper
+
+        meta = json.loads(base64.b64decode(data.encode()).decode())
+        if meta.get("format") != self.FORMAT:
+            raise ValueError(f"not a {self.FORMAT} dump (format {meta.get('format')!r})")
+        arr = np.load(io.BytesIO(base64.b64decode(meta["arrays"])), allow_pickle=False)
+        hyp = MixedGPHyper(params=arr["params"], noise=meta["noise"], constant=meta["constant"],
+                           y_mean=meta["y_mean"], y_std=meta["y_std"])
         self._set_state(arr["X"], arr["y"], arr["lo"], arr["hi"], meta["kind"], hyp)
 
 
@@ -497,9 +672,11 @@ def union_rows(Xs):
 
 
 def map(data_model):
-    """bofire/surrogates/mapper.py:21-44 (SingleTaskGPSurrogate only)."""
+    """bofire/surrogates/mapper.py:21-44 (SingleTaskGPSurrogate and MixedSingleTaskGPSurrogate)."""
     if isinstance(data_model, dm.SingleTaskGPSurrogate):
         return SingleTaskGPSurrogate(data_model)
+    if isinstance(data_model, dm.MixedSingleTaskGPSurrogate):
+        return MixedSingleTaskGPSurrogate(data_model)
     if isinstance(data_model, dm.BotorchSurrogates):
         return BotorchSurrogates(data_model)
     raise NotImplementedError(f"{type(data_model).__name__} is out of scope for the MI355X build")

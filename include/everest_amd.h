@@ -71,6 +71,31 @@ int evr_kernel_lengthscale_grad(void* stream, int kind, int B, int n, int d, con
 int evr_gp_mll_terms(void* stream, int B, int n, const double* L, const double* Linv,
                      const double* r, const double* alpha, double* out);
 
+/* ---- mixed continuous / categorical kernel ([upstream] BoTorch MixedSingleTaskGP, built by
+ * bofire/surrogates/mixed_single_task_gp.py:46-112) --------------------------------------
+ *   K(x, x') = s_sum (k_c(r1) + s_cat h1) + s_prod k_c(r2) h2
+ *   r_t^2 = sum_k ((xc_k - xc'_k) / ls_t,k)^2                              t = 1, 2
+ *   h_t   = exp(-(1 / nc) sum_f [c_f != c'_f] / lam_t,f)   (CategoricalKernel, ARD over the features)
+ * k_c: one family 0..3 (kind) for every member, with the d2 < 1e-30 convention of the
+ * continuous kernels.  Inputs, shared by the B members: Xc (n x dc, normalised continuous
+ * columns) and C (n x nc, int32 category codes).  Member b reads params + b P,
+ * P = 2 dc + 2 nc + 3: [ls1 (dc) | ls2 (dc) | lam1 (nc) | lam2 (nc) | s_sum | s_cat | s_prod].
+ * Supported: 1 <= dc <= 32, 1 <= nc <= 8 (any cardinality); anything else is an error.
+ *
+ * K: B x n1 x n2; diag_add (B, or NULL) is added where i == j (meaningful for the train
+ * matrix only).  Explicit differences, no distance expansion.  Every entry is computed from an
+ * expression that does not depend on the order of its two points (no tile is mirrored): with
+ * X2 = X1 the result is bitwise symmetric, and the train matrix is the cross call's. */
+int evr_mixed_kernel_matrix(void* stream, int kind, int B, int n1, int n2, int dc, int nc, const double* X1c,
+                            const int* C1, const double* X2c, const int* C2, const double* params,
+                            const double* diag_add, double* K);
+/* g[b][p] = sum_{i,j} W[b][i][j] dK_b[i][j] / dparams_p for all P parameters in one pass over W
+ * (B x n x n, need not be symmetric).  work: B*n*P doubles (per-row partials, summed in a
+ * fixed order: bitwise reproducible).  A wave per row up to dc = 16 (instantiations for
+ * dc <= 8 and dc <= 16), a workgroup per row above. */
+int evr_mixed_kernel_param_grad(void* stream, int kind, int B, int n, int dc, int nc, const double* Xc, const int* C,
+                                const double* params, const double* W, double* g, double* work);
+
 /* Native MLL plan for the GP fit: B exact GPs sharing the normalised inputs Xn (n x d,
  * device, must outlive the plan) with standardised targets Y (B x n, device, copied).  One
  * evr_mll_plan_eval is one hipGraph launch computing, per member b, with params (host) =
