@@ -82,6 +82,18 @@ class EvrParego(ctypes.Structure):
     ]
 
 
+class EvrMult(ctypes.Structure):
+    _fields_ = [
+        ("log", c_int), ("tau_relu", c_double), ("tau_max", c_double), ("best", c_void_p), ("best_stride", c_int),
+        ("n_fac", c_int),
+        ("fac_out", c_void_p), ("fac_kind", c_void_p), ("fac_w", c_void_p), ("fac_p0", c_void_p),
+        ("fac_p1", c_void_p), ("fac_p2", c_void_p),
+        ("n_add", c_int),
+        ("add_out", c_void_p), ("add_kind", c_void_p), ("add_w", c_void_p), ("add_p0", c_void_p),
+        ("add_p1", c_void_p), ("add_p2", c_void_p),
+    ]
+
+
 class EvrReward(ctypes.Structure):
     _fields_ = [
         ("mode", c_int), ("ucb_scale", c_double), ("tau", c_double), ("best", c_void_p),
@@ -218,6 +230,11 @@ _SIGS = {
                                        c_int, c_int], c_longlong),
     "evr_qparego_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
                           POINTER(EvrParego), c_int] + [c_void_p] * 5, c_int),
+    "evr_mult_scan": ([c_void_p, c_int, c_int, c_int, c_int, POINTER(EvrMult)] + [c_void_p] * 5, c_int),
+    "evr_qmult_workspace_doubles": ([POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
+                                     c_int, c_int], c_longlong),
+    "evr_qmult_eval": ([c_void_p, POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
+                        POINTER(EvrMult), c_int] + [c_void_p] * 5, c_int),
     "evr_reward_scan": ([c_void_p, c_int, c_int, c_int, c_int, POINTER(EvrReward)] + [c_void_p] * 5, c_int),
     "evr_qreward_workspace_doubles": ([POINTER(EvrQnehviState), POINTER(EvrQnGeneral), POINTER(EvrQnehviModel),
                                        c_int, c_int], c_longlong),

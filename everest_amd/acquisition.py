@@ -1278,7 +1278,8 @@ class _SoboAcqf(_NeiAcqf):
     the reduction over q, so the hypervolume chain's q-subset weighting does not apply.
     Subclasses set gp, dev, S, M, nb, spec and the incumbent(s) ``best`` and call _finish; the
     evaluation is _NeiAcqf's through the hooks below.  The spec decides the scan: an ops.SoboSpec runs evr_qsobo_eval, an ops.ParegoSpec (the
-    QParego* classes) evr_qparego_eval with the augmented Chebyshev scan of parego_scan.hip;
+    QParego* classes) evr_qparego_eval with the augmented Chebyshev scan of parego_scan.hip, an
+    ops.MultSpec (the QMult* classes) evr_qmult_eval with the product scan of mult_scan.hip;
     construction, incumbents and pruning only use the spec's utility / feasible.
 
     BoTorch is not importable offline: the incumbent's mean - 6 sigma fallback and the constrained
@@ -1288,6 +1289,11 @@ class _SoboAcqf(_NeiAcqf):
     def _parego(self) -> bool:
         """Dispatch on the spec: an ops.ParegoSpec runs the augmented Chebyshev scan."""
         return isinstance(self.spec, ops.ParegoSpec)
+
+    @property
+    def _mult(self) -> bool:
+        """Dispatch on the spec: an ops.MultSpec runs the multiplicative / additive scan."""
+        return isinstance(self.spec, ops.MultSpec)
 
     @staticmethod
     def _check_model(gp: GPBatch, spec: "ops.SoboSpec", name: str):
@@ -1300,6 +1306,8 @@ class _SoboAcqf(_NeiAcqf):
         return self.spec.struct(self.log_acqf, self.tau_relu, self.tau_max, self.best)
 
     def _chain_eval(self):
+        if self._mult:
+            return ops.qmult_eval
         return ops.qparego_eval if self._parego else ops.qsobo_eval
 
     def _g(self, qq: int):
@@ -1317,10 +1325,15 @@ class _SoboAcqf(_NeiAcqf):
         head = (state, model, self.log_acqf, self.tau_relu, self.tau_max, self.best)
         if self._parego:
             return torch.classes.everest_amd.QparegoAcq(*head, self.spec.alpha, *self._tables(), keep)
+        if self._mult:
+            rows = lambda r: torch.tensor(r, dtype=torch.float64).reshape(-1, 6)  # noqa: E731
+            return torch.classes.everest_amd.QmultAcq(*head, rows(self.spec.factors), rows(self.spec.addends), keep)
         return torch.classes.everest_amd.QsoboAcq(*head, *self._tables(), keep)
 
     def _function(self):
-        from .torch_ops import QparegoFunction, QsoboFunction
+        from .torch_ops import QmultFunction, QparegoFunction, QsoboFunction
+        if self._mult:
+            return QmultFunction
         return QparegoFunction if self._parego else QsoboFunction
 
 
@@ -1578,6 +1591,41 @@ class QParegoLogEI(QSoboLogEI):
 
     def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, spec: "ops.ParegoSpec", **kw):
         _need_parego(spec, "QParegoLogEI")
+        super().__init__(gp, X_train_raw, spec, **kw)
+
+
+def _need_mult(spec, name: str):
+    if not isinstance(spec, ops.MultSpec):
+        raise TypeError(f"{name} needs an ops.MultSpec, got {type(spec).__name__}")
+
+
+class QMultNEI(QSoboNEI):
+    """Device qNEI of MultiplicativeSoboStrategy / MultiplicativeAdditiveSoboStrategy — [upstream]
+    get_acquisition_function("qNEI") over a GenericMCObjective of
+    get_multiplicative_botorch_objective / get_multiplicative_additive_objective
+    (bofire/strategies/predictives/sobo.py:225-284): the QSoboNEI construction (baseline root,
+    prune, per-sample incumbent, M, pending points, base samples) with the utility
+    u(y) = prod_k g_k ** w_k * (1 + sum_a w_a g_a) of ``spec`` (ops.MultSpec) and the scan of
+    mult_scan.hip.  Parity-unpinned like QSoboNEI."""
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, X_baseline_raw: np.ndarray, spec: "ops.MultSpec",
+                 **kw):
+        _need_mult(spec, type(self).__name__)
+        super().__init__(gp, X_train_raw, X_baseline_raw, spec, **kw)
+
+
+class QMultLogNEI(QMultNEI):
+    """Device qLogNEI (fat = True) of the multiplicative strategies: QMultNEI with the log scan."""
+
+    _LOG = True
+
+
+class QMultLogEI(QSoboLogEI):
+    """Device qLogEI (``log=False``: qEI) of the multiplicative strategies: the QSoboLogEI
+    construction with the utility of ``spec`` (ops.MultSpec)."""
+
+    def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, spec: "ops.MultSpec", **kw):
+        _need_mult(spec, "QMultLogEI")
         super().__init__(gp, X_train_raw, spec, **kw)
 
 

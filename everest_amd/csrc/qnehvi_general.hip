@@ -1227,6 +1227,8 @@ int parego_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const ev
                        const int* flags, const double* gout, double* acq, double* dY);
 int reward_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_reward* rw, const double* Y,
                        const int* flags, const double* gout, double* acq, double* dY);
+int mult_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_mult* mt, const double* Y,
+                     const int* flags, const double* gout, double* acq, double* dY);
 
 struct QnLayout {
   size_t Kx, R, P, Wf, Y, Lq, flags, dY, cf, dKqq, cm, gR, dKx, Wb, kg, total;
@@ -1413,6 +1415,23 @@ int evr_qreward_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_gen
   return qn_chain("evr_qreward_eval", s, stm, g, md, b, X, work, acq, dX,
                   [&](int q, int m, int S, const double* Y, const int* flags, double* dY) {
                     return reward_scan_launch(s, q, m, S, b, rw, Y, flags, gout, acq, dY);
+                  });
+}
+
+// qMult*: the chain with the multiplicative / multiplicative-additive scan of mult_scan.hip.
+long long evr_qmult_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                      const evr_qnehvi_model* md, int b, int backward) {
+  return qn_workspace_doubles(stm, g, md, b, backward);
+}
+
+int evr_qmult_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                   const evr_mult* mt, int b, const double* X, const double* gout, double* work, double* acq,
+                   double* dX) {
+  EVR_CHECK(stm && g && md && mt, "evr_qmult_eval: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  return qn_chain("evr_qmult_eval", s, stm, g, md, b, X, work, acq, dX,
+                  [&](int q, int m, int S, const double* Y, const int* flags, double* dY) {
+                    return mult_scan_launch(s, q, m, S, b, mt, Y, flags, gout, acq, dY);
                   });
 }
 

@@ -8,9 +8,9 @@
 // TORCH_CHECK (-> RuntimeError) and raises the C-ABI's evr_last_error() on failure.
 //
 // Structure: the dense ops, then QnehviAcq (the hypervolume chain with its plan cache), then
-// ChainAcq — the one host path of the single-objective acquisitions, whose four registered
-// classes (QneiAcq, QsoboAcq, QparegoAcq, QrewardAcq) add only their constructor arguments,
-// their parameter struct and the names of their two C functions.
+// ChainAcq — the one host path of the single-objective acquisitions, whose five registered
+// classes (QneiAcq, QsoboAcq, QparegoAcq, QmultAcq, QrewardAcq) add only their constructor
+// arguments, their parameter struct and the names of their two C functions.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -473,6 +473,37 @@ struct QparegoAcq : ChainAcq<evr_parego, evr_qparego_workspace_doubles, evr_qpar
   }
 };
 
+// the multiplicative / multiplicative-additive qNEI / qLogNEI / qLogEI / qEI (mult_scan.hip);
+// factors (n_fac x 6, may be empty) and addends (n_add x 6, may be empty): (out, kind, w, p0, p1, p2)
+struct QmultAcq : ChainAcq<evr_mult, evr_qmult_workspace_doubles, evr_qmult_eval> {
+  ScanTables fac, add;
+
+  QmultAcq(const at::Tensor& stm_b, const at::Tensor& md_b, bool log_, double tau_relu, double tau_max,
+           const at::Tensor& best_, const at::Tensor& factors_, const at::Tensor& addends_,
+           std::vector<at::Tensor> keep_)
+      : ChainAcq("QmultAcq", "qmult", stm_b, md_b, best_, true, std::move(keep_)),
+        fac(cls, factors_, at::Tensor(at::empty({0, 4}, at::kDouble)), 0),
+        add(cls, addends_, at::Tensor(at::empty({0, 4}, at::kDouble)), 0) {
+    TORCH_CHECK(fac.to.size() + add.to.size() >= 1 && fac.to.size() + add.to.size() <= EVR_SOBO_MAX_TERMS, cls,
+                ": 1..", EVR_SOBO_MAX_TERMS, " factors and addends in all");
+    improvement(log_, tau_relu, tau_max);
+    par.n_fac = (int)fac.to.size();
+    par.fac_out = fac.to.data();
+    par.fac_kind = fac.tk.data();
+    par.fac_w = fac.tc[0].data();
+    par.fac_p0 = fac.tc[1].data();
+    par.fac_p1 = fac.tc[2].data();
+    par.fac_p2 = fac.tc[3].data();
+    par.n_add = (int)add.to.size();
+    par.add_out = add.to.data();
+    par.add_kind = add.tk.data();
+    par.add_w = add.tc[0].data();
+    par.add_p0 = add.tc[1].data();
+    par.add_p1 = add.tc[2].data();
+    par.add_p2 = add.tc[3].data();
+  }
+};
+
 // qSR / qUCB / qPI over several model outputs (reward_scan.hip); mode: EVR_REWARD_*; best: one
 // double (read by qPI only); terms / cons as in QsoboAcq
 struct QrewardAcq : ChainAcq<evr_reward, evr_qreward_workspace_doubles, evr_qreward_eval> {
@@ -523,6 +554,7 @@ TORCH_LIBRARY(everest_amd, m) {
   using T = at::Tensor;
   using Keep = std::vector<at::Tensor>;
   def_chain<QrewardAcq, T, T, int64_t, double, double, double, T, T, T, Keep>(m, "QrewardAcq");
+  def_chain<QmultAcq, T, T, bool, double, double, T, T, T, Keep>(m, "QmultAcq");
   def_chain<QparegoAcq, T, T, bool, double, double, T, double, T, T, Keep>(m, "QparegoAcq");
   def_chain<QsoboAcq, T, T, bool, double, double, T, T, T, Keep>(m, "QsoboAcq");
   def_chain<QneiAcq, T, T, bool, double, double, T, double, double, Keep>(m, "QneiAcq");
@@ -546,6 +578,8 @@ TORCH_LIBRARY(everest_amd, m) {
   m.def("qsobo_forward_backward(__torch__.torch.classes.everest_amd.QsoboAcq acq, Tensor X) -> (Tensor, Tensor)");
   m.def("qparego_forward(__torch__.torch.classes.everest_amd.QparegoAcq acq, Tensor X) -> Tensor");
   m.def("qparego_forward_backward(__torch__.torch.classes.everest_amd.QparegoAcq acq, Tensor X) -> (Tensor, Tensor)");
+  m.def("qmult_forward(__torch__.torch.classes.everest_amd.QmultAcq acq, Tensor X) -> Tensor");
+  m.def("qmult_forward_backward(__torch__.torch.classes.everest_amd.QmultAcq acq, Tensor X) -> (Tensor, Tensor)");
   m.def("qreward_forward(__torch__.torch.classes.everest_amd.QrewardAcq acq, Tensor X) -> Tensor");
   m.def("qreward_forward_backward(__torch__.torch.classes.everest_amd.QrewardAcq acq, Tensor X) -> (Tensor, Tensor)");
 }
@@ -565,6 +599,8 @@ TORCH_LIBRARY_IMPL(everest_amd, CUDA, m) {
   m.impl("qsobo_forward_backward", &chain_forward_backward<QsoboAcq>);
   m.impl("qparego_forward", &chain_forward<QparegoAcq>);
   m.impl("qparego_forward_backward", &chain_forward_backward<QparegoAcq>);
+  m.impl("qmult_forward", &chain_forward<QmultAcq>);
+  m.impl("qmult_forward_backward", &chain_forward_backward<QmultAcq>);
   m.impl("qreward_forward", &chain_forward<QrewardAcq>);
   m.impl("qreward_forward_backward", &chain_forward_backward<QrewardAcq>);
 }

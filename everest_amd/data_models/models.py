@@ -524,6 +524,60 @@ class AdditiveSoboStrategy(BotorchStrategy):
         return v
 
 
+def _check_adaptable_weights(self):
+    """bofire/data_models/strategies/predictives/sobo.py:78-93 (_CheckAdaptableWeightsMixin): the
+    weights are divided by the smallest one, which needs w >= 1e-8.  Deviation: the reference
+    raises a TypeError here, from building its pydantic.ValidationError with a message alone;
+    this raises the ValueError it means to, with the same message."""
+    for f in self.domain.outputs.get_by_objective().features:
+        if f.objective.w < 1e-8:
+            raise ValueError(f"Weight transformation to (1, inf) requires w>=1e-8 . Violated by feature {f.key}.")
+    return self
+
+
+class MultiplicativeSoboStrategy(BotorchStrategy):
+    """bofire/data_models/strategies/predictives/sobo.py:96-105: the product of the objectives,
+    each raised to its weight (weights divided by the smallest, so in [1, inf))."""
+    type: Literal["MultiplicativeSoboStrategy"] = "MultiplicativeSoboStrategy"
+    acquisition_function: AnySingleObjectiveAcquisitionFunction = Field(default_factory=qLogNEI)
+
+    @field_validator("domain")
+    @classmethod
+    def validate_is_multiobjective(cls, v):
+        if len(v.outputs.get_by_objective(Objective)) < 2:
+            raise ValueError("Multiplicative SOBO strategy requires at least 2 outputs with objectives. Consider "
+                             "SOBO strategy instead.")
+        return v
+
+    @model_validator(mode="after")
+    def check_adaptable_weights(self):
+        return _check_adaptable_weights(self)
+
+
+class MultiplicativeAdditiveSoboStrategy(BotorchStrategy):
+    """bofire/data_models/strategies/predictives/sobo.py:108-135: multiplicative (strict) and
+    additive (non-strict) objectives, f1^w1 * f2^w2 * (1 + f3*w3 + f4*w4) for the outputs named in
+    ``additive_features``.  A single objective is accepted.  ``use_output_constraints`` is carried
+    as in the reference, whose strategy never reads it."""
+    type: Literal["MultiplicativeAdditiveSoboStrategy"] = "MultiplicativeAdditiveSoboStrategy"
+    acquisition_function: AnySingleObjectiveAcquisitionFunction = Field(default_factory=qLogNEI)
+    use_output_constraints: bool = True
+    additive_features: List[str] = Field(default_factory=list)
+
+    @field_validator("additive_features")
+    @classmethod
+    def validate_additive_features(cls, v, info):
+        domain = info.data["domain"]
+        for feature in v:
+            if feature not in domain.outputs.get_keys():
+                raise ValueError(f"Feature {feature} is not an output feature of the domain.")
+        return v
+
+    @model_validator(mode="after")
+    def check_adaptable_weights(self):
+        return _check_adaptable_weights(self)
+
+
 class ActiveLearningStrategy(BotorchStrategy):
     """bofire/data_models/strategies/predictives/active_learning.py:14-62: pure exploration, the
     candidates that most reduce the integrated posterior variance.  Every objective type is
@@ -541,5 +595,6 @@ class ActiveLearningStrategy(BotorchStrategy):
 
 
 AnyStrategy = Annotated[Union[QnehviStrategy, QehviStrategy, MoboStrategy, QparegoStrategy, SoboStrategy,
-                              AdditiveSoboStrategy, ActiveLearningStrategy, RandomStrategy],
+                              AdditiveSoboStrategy, MultiplicativeSoboStrategy, MultiplicativeAdditiveSoboStrategy,
+                              ActiveLearningStrategy, RandomStrategy],
                         Field(discriminator="type")]

@@ -893,6 +893,84 @@ def qparego_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehvi
     return _utility_eval("evr_qparego", stm, g, model, pg, X, backward, gout)
 
 
+class MultSpec:
+    """Multiplicative / multiplicative-additive utility over model outputs for the scan of
+    mult_scan.hip (evr_mult):
+
+        u(y) = [prod_k g_k(y[out_k]) ** w_k] * [1 + sum_a w_a g_a(y[out_a])]
+
+    factors / addends: [(output, kind, w, p0, p1, p2)] with the kinds and parameters of
+    ``SoboSpec``; either list may be empty, not both, and they hold 8 rows at most together.  A
+    factor's weight is finite and >= 1 (the normalised weights of bofire/utils/torch_tools.py:
+    655-657), an addend's finite.  ``**`` is C pow (torch.pow(tensor, float)): a negative base is
+    real with an integer-valued exponent and NaN with any other.  There are no output
+    constraints.  The class has ``SoboSpec``'s interface (struct / utility / feasible /
+    constraints / m_model)."""
+
+    def __init__(self, m_model: int, factors, addends=()):
+        self.m_model = int(m_model)
+        row = lambda r: (int(r[0]), int(r[1])) + tuple(float(v) for v in r[2:6])  # noqa: E731
+        self.factors = [row(r) for r in factors]
+        self.addends = [row(r) for r in addends]
+        self.constraints = []
+        if not 1 <= len(self.factors) + len(self.addends) <= 8:
+            raise ValueError("mult scan: 1..8 factors and addends in all")
+        for what, rows in (("factor", self.factors), ("addend", self.addends)):
+            for o, k, w, *_ in rows:
+                if not 0 <= o < self.m_model:
+                    raise ValueError(f"mult scan: output index {o} outside the model's {self.m_model} outputs")
+                if k not in (OBJ_AFFINE, OBJ_CLOSE_TO_TARGET, OBJ_SIGMOID, OBJ_TARGET):
+                    raise ValueError(f"mult scan: {what} kind {k}")
+                if not math.isfinite(w) or (what == "factor" and w < 1.0):
+                    raise ValueError(f"mult scan: {what} weight {w} (finite; a factor's >= 1 after normalisation)")
+        # an empty group keeps one placeholder row: the pointers stay valid, the count says 0
+        pad = [(0, OBJ_AFFINE, 1.0, 0.0, 0.0, 0.0)]
+        self._farrs, _ = _table_arrays(self.factors or pad, [])
+        self._aarrs, _ = _table_arrays(self.addends or pad, [])
+
+    @property
+    def terms(self):
+        """Factors, then addends (the device table's order)."""
+        return self.factors + self.addends
+
+    def struct(self, log: bool, tau_relu: float, tau_max: float, best: torch.Tensor) -> "_native.EvrMult":
+        """evr_mult over ``best`` (device; S per-sample incumbents, or one value: stride 0).  The
+        struct points into this spec's host arrays and into ``best``: keep both alive."""
+        mt = _improvement(_native.EvrMult(), log, tau_relu, tau_max, best)
+        mt.n_fac, mt.n_add = len(self.factors), len(self.addends)
+        (mt.fac_out, mt.fac_kind, mt.fac_w, mt.fac_p0, mt.fac_p1, mt.fac_p2) = (a.ctypes.data for a in self._farrs)
+        (mt.add_out, mt.add_kind, mt.add_w, mt.add_p0, mt.add_p1, mt.add_p2) = (a.ctypes.data for a in self._aarrs)
+        return mt
+
+    def utility(self, Y):
+        """u of model-output rows Y (... x m_model; numpy array or torch tensor), multiplied and
+        summed up in the reference's order: 1 * g_0 ** w_0 * ..., then 1 + g_a w_a + ..."""
+        add = 1.0
+        for o, k, w, a, b, c in self.addends:
+            add = add + SoboSpec._term(k, a, b, c, Y[..., o]) * w
+        mul = 1.0
+        for o, k, w, a, b, c in self.factors:
+            mul = mul * SoboSpec._term(k, a, b, c, Y[..., o]) ** w
+        return mul * add
+
+    feasible = SoboSpec.feasible
+
+
+def mult_scan(Y: torch.Tensor, q: int, best: torch.Tensor, spec: MultSpec, log: bool = False,
+              tau_relu: float = 1e-6, tau_max: float = 1e-2, flags: Optional[torch.Tensor] = None,
+              gout: Optional[torch.Tensor] = None, backward: bool = False):
+    """Multiplicative / multiplicative-additive scan alone (evr_mult_scan); arguments and results as
+    ``sobo_scan``."""
+    return _utility_scan("evr_mult_scan", Y, q, best, spec, log, tau_relu, tau_max, flags, gout, backward)
+
+
+def qmult_eval(stm: EvrQnehviState, g: EvrQnGeneral, model: "_native.EvrQnehviModel", mt: "_native.EvrMult",
+               X: torch.Tensor, backward: bool, gout: Optional[torch.Tensor] = None):
+    """The multiplicative strategies' qNEI, qLogNEI, qLogEI, qEI over m model outputs
+    (evr_qmult_eval): X (b*q) x d raw candidates -> acq (b) [, dX (b*q) x d]."""
+    return _utility_eval("evr_qmult", stm, g, model, mt, X, backward, gout)
+
+
 REWARD_SR, REWARD_UCB, REWARD_PI = 0, 1, 2
 
 

@@ -20,7 +20,8 @@ import torch
 
 from . import data_models as dm
 from . import ops
-from .acquisition import (QNegIntPosVar, QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QNEHVI, QNEI, QParegoLogEI,
+from .acquisition import (QNegIntPosVar, QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI, QLogNEHVI, QLogNEI, QMultLogEI,
+                          QMultLogNEI, QMultNEI, QNEHVI, QNEI, QParegoLogEI,
                           QParegoLogNEI, QParegoNEI, QSoboLogEI, QSoboLogNEI, QSoboNEI, QSoboPI, QSoboSR, QSoboUCB,
                           get_infeasible_cost, prefetch_scramble)
 from .data_models.domain import CloseToTargetObjective, MaximizeObjective, MinimizeObjective
@@ -806,6 +807,50 @@ def sobo_objective_spec(outputs, output_keys: Sequence[str], experiments: Option
     return terms, constraints
 
 
+def mult_objective_spec(outputs, output_keys: Sequence[str], experiments: Optional[pd.DataFrame] = None,
+                        additive_features: Optional[Sequence[str]] = None, exclude_constraints: bool = False):
+    """(factors, addends) of the multiplicative utilities over the model outputs ``output_keys``
+    (host only, no device), rows (output, kind, w, p0, p1, p2) for ``ops.MultSpec``.  This is the
+    reference's behaviour as written:
+
+    _callables_and_weights (bofire/utils/torch_tools.py:598-659) walks the outputs in order, skips
+    those without an objective and, with ``exclude_constraints``, those with a
+    ConstrainedObjective, BEFORE it divides every weight by the smallest of the remaining list
+    (adapt_weights_to_1_inf: the smallest weight becomes exactly 1.0).
+    get_multiplicative_botorch_objective (:662-675, ``exclude_constraints=False``): every objective
+    is a factor, sigmoid / target / moving-sigmoid ones included.
+    get_multiplicative_additive_objective (:730-806, ``exclude_constraints=True``, its default,
+    which MultiplicativeAdditiveSoboStrategy never overrides): the constrained objectives have no
+    effect at all (the strategy returns no output constraints either); the rest is split by
+    ``additive_features``, and a name there that matches no listed output matches nothing.  Either
+    group may come out empty.  An empty list (every objective constrained) raises ValueError, where
+    the reference fails in min([])."""
+    keys = list(output_keys)
+    additive = list(additive_features or [])
+    listed = []
+    for f in outputs.get().features:
+        obj = getattr(f, "objective", None)
+        if obj is None:
+            continue
+        if exclude_constraints and isinstance(obj, dm.ConstrainedObjective):
+            continue
+        listed.append(f)
+    if not listed:
+        raise ValueError("no objective is left for the multiplicative utility (every objective is a constrained "
+                         "objective, which this utility leaves out)")
+    min_w = min(f.objective.w for f in listed)
+    factors, addends = [], []
+    for f in listed:
+        x_adapt = None
+        if isinstance(f.objective, dm.MovingMaximizeSigmoidObjective):
+            if experiments is None:
+                raise ValueError("MovingMaximizeSigmoidObjective needs the experiments")
+            x_adapt = outputs.preprocess_experiments_one_valid_output(f.key, experiments)[f.key].values
+        term = sobo_term(f.objective, keys.index(f.key), f.objective.w / min_w, x_adapt)
+        (addends if f.key in additive else factors).append(term)
+    return factors, addends
+
+
 def reward_constraint_handling(af, constraints) -> str:
     """How qSR / qUCB / qPI treat the output constraints that ``sobo_objective_spec`` yields (host
     only): "absorbed" — qSR and qUCB fold them into the objective with the infeasible cost M
@@ -927,6 +972,62 @@ class AdditiveSoboStrategy(SoboStrategy):
     constraints, without it they enter the sum as sigmoid / target terms."""
 
     _additive = True
+
+
+_MULT_ACQFS = "qLogNEI(), qNEI(), qLogEI() or qEI()"
+
+
+class MultiplicativeSoboStrategy(SoboStrategy):
+    """bofire/strategies/predictives/sobo.py:225-252 — u = prod_k g_k ** w_k over EVERY objective
+    (the constrained ones are factors, there are no output constraints), weights divided by the
+    smallest.  Runs QMultLogNEI (the data model's default) / QMultNEI / QMultLogEI over all model
+    outputs (mult_scan.hip).  qSR, qUCB and qPI are not built for this utility: the reward scan sums
+    terms."""
+
+    _exclude_constraints = False
+    additive_features: Sequence[str] = ()
+
+    def _mult_spec(self, output_keys: Optional[Sequence[str]] = None) -> ops.MultSpec:
+        """The utility over the model outputs (``mult_objective_spec``)."""
+        keys = list(self.model.output_keys) if output_keys is None else list(output_keys)
+        factors, addends = mult_objective_spec(self.domain.outputs, keys, self.experiments,
+                                               additive_features=self.additive_features,
+                                               exclude_constraints=self._exclude_constraints)
+        return ops.MultSpec(len(keys), factors, addends)
+
+    def _get_acqfs(self, n):
+        af = self.acquisition_function
+        if not isinstance(af, (dm.qEI, dm.qLogEI, dm.qNEI, dm.qLogNEI)):
+            raise NotImplementedError(f"{type(af).__name__} has no device kernel for {type(self).__name__}; use "
+                                      f"{_MULT_ACQFS}")
+        spec = self._mult_spec()
+        X_train, X_pending = self.get_acqf_input_tensors()
+        S = int(af.n_mc_samples)
+        if isinstance(af, (dm.qNEI, dm.qLogNEI)):
+            # seed order of _get_general_acqfs: prune seed (when pruning), then sampler seed
+            prune_seed = self._draw_seed() if af.prune_baseline else 0
+            sampler_seed = self._draw_seed()
+            cls = QMultLogNEI if isinstance(af, dm.qLogNEI) else QMultNEI
+            acqf = cls(self.model, self.model.X_raw, X_train, spec, S=S, sampler_seed=sampler_seed,
+                       prune_baseline=af.prune_baseline, prune_seed=prune_seed, X_pending_raw=X_pending)
+        else:
+            acqf = QMultLogEI(self.model, X_train, spec, S=S, seed=self._draw_seed(), X_pending_raw=X_pending,
+                              log=isinstance(af, dm.qLogEI))
+        self.last_acqf = acqf
+        return [acqf]
+
+
+class MultiplicativeAdditiveSoboStrategy(MultiplicativeSoboStrategy):
+    """bofire/strategies/predictives/sobo.py:255-284 — u = prod_k g_k ** w_k * (1 + sum_a w_a g_a):
+    the outputs named in ``additive_features`` enter the bracket, the others the product.  As the
+    reference is written, outputs with a ConstrainedObjective are left out altogether
+    (``mult_objective_spec``) and ``use_output_constraints`` is not read."""
+
+    _exclude_constraints = True
+
+    def __init__(self, data_model, dist=None, **kwargs):
+        super().__init__(data_model, dist=dist, **kwargs)
+        self.additive_features = list(data_model.additive_features)
 
 
 PAREGO_ALPHA = 0.05      # [upstream] get_chebyshev_scalarization(alpha=0.05)
@@ -1198,9 +1299,18 @@ STRATEGY_MAP = {
 }
 
 
+# The two multiplicative strategies are registered in a table of their own, which ``map`` reads as
+# well: tests/test_sobo_datamodels.py pins the content of STRATEGY_MAP as it stood before they existed.
+# Merge the two tables once that test may change.
+MULT_STRATEGY_MAP = {
+    dm.MultiplicativeSoboStrategy: MultiplicativeSoboStrategy,
+    dm.MultiplicativeAdditiveSoboStrategy: MultiplicativeAdditiveSoboStrategy,
+}
+
+
 def map(data_model, **kwargs):
     """bofire/strategies/mapper.py:7-14."""
-    cls = STRATEGY_MAP.get(type(data_model))
+    cls = STRATEGY_MAP.get(type(data_model)) or MULT_STRATEGY_MAP.get(type(data_model))
     if cls is None:
         raise NotImplementedError(f"{type(data_model).__name__} is out of scope for the MI355X build")
     return cls(data_model, **kwargs) if cls is not RandomStrategy else cls(data_model)

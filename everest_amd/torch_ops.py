@@ -17,12 +17,14 @@ AcquisitionFunction.forward protocols called at bofire/strategies/predictives/bo
     torch.ops.everest_amd.qsobo_forward / qsobo_forward_backward   (scalarised / output-constrained SOBO)
     torch.classes.everest_amd.QparegoAcq(state, model, log, tau_relu, tau_max, best, alpha, terms, constraints, keep)
     torch.ops.everest_amd.qparego_forward / qparego_forward_backward   (qParEGO: augmented Chebyshev utility)
+    torch.classes.everest_amd.QmultAcq(state, model, log, tau_relu, tau_max, best, factors, addends, keep)
+    torch.ops.everest_amd.qmult_forward / qmult_forward_backward   (multiplicative / multiplicative-additive SOBO)
     torch.classes.everest_amd.QrewardAcq(state, model, mode, ucb_scale, tau, infeasible_cost, best, terms,
                                          constraints, keep)
     torch.ops.everest_amd.qreward_forward / qreward_forward_backward   (qSR, qUCB, qPI)
 
-The five autograd wrappers (QnehviFunction, QneiFunction, QsoboFunction, QparegoFunction,
-QrewardFunction) are instances of one body, _chain_function(prefix), that differ in the operator
+The six autograd wrappers (QnehviFunction, QneiFunction, QsoboFunction, QparegoFunction,
+QmultFunction, QrewardFunction) are instances of one body, _chain_function(prefix), that differ in the operator
 prefix only.
 
 No fallback: a missing library raises NativeLibraryError."""
@@ -83,4 +85,5 @@ QneiFunction = _chain_function("qnei", "acq = qNEI / qLogNEI / qLogEI(X), X b x 
 QsoboFunction = _chain_function("qsobo", "acq = QSoboNEI / QSoboLogNEI / QSoboLogEI(X), X b x q x d, on a QsoboAcq.")
 QparegoFunction = _chain_function("qparego",
                                   "acq = QParegoNEI / QParegoLogNEI / QParegoLogEI(X), X b x q x d, on a QparegoAcq.")
+QmultFunction = _chain_function("qmult", "acq = QMultNEI / QMultLogNEI / QMultLogEI(X), X b x q x d, on a QmultAcq.")
 QrewardFunction = _chain_function("qreward", "acq = QSoboSR / QSoboUCB / QSoboPI(X), X b x q x d, on a QrewardAcq.")

@@ -684,6 +684,56 @@ int evr_qreward_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_gen
                      const evr_reward* rw, int b, const double* X, const double* gout, double* work, double* acq,
                      double* dX);
 
+/* ---- multiplicative / multiplicative-additive utility scan (mult_scan.hip) ------------------
+ * The step between the joint samples Y of q-point candidates and dY for the utility
+ *   u(y) = [ prod_{k factor} g_k(y[out_k]) ** w_k ] * [ 1 + sum_{a addend} w_a * g_a(y[out_a]) ]
+ * of BoFire's MultiplicativeSoboStrategy (no addends) and MultiplicativeAdditiveSoboStrategy
+ * (bofire/utils/torch_tools.py:662-675, 730-806; bofire/strategies/predictives/sobo.py:225-284),
+ * without output constraints.  ** is C pow: a negative base is real with an integer-valued
+ * exponent and NaN with any other.  Term kinds and their p0 / p1 / p2: the four EVR_OBJ_* of
+ * evr_sobo.  The reductions over the q points and the samples are evr_sobo_scan's at n_con = 0;
+ * Y / dY, flags, best / best_stride, gout and the plain-mode subgradients are evr_sobo_scan's.
+ * Backward: d u / d g_k = w_k pow(g_k, w_k - 1) * prod_{s != k} g_s ** w_s * A, d u / d g_a =
+ * w_a * P (A the bracket, P the product); the product of the others is formed from the others,
+ * never by division, so an exactly zero factor keeps the slope of the rest.  dY is written in
+ * full, outputs nothing reads get exact zeros.  A candidate with a NaN utility in any (sample,
+ * point) gets acq = NaN (its dY columns are unspecified); the others are unaffected.  The table
+ * arrays are HOST arrays (copied into the launch); best is on the device.  Refused: table sizes
+ * outside the limits, an output index outside the model, an unknown kind, a weight that is not
+ * finite or (factor) below 1, tau <= 0 in log mode, best_stride not 0 or 1.  Forward and backward
+ * are ONE launch; no atomics; results are bitwise reproducible, and the forward-only launch gives
+ * the bits of the backward one. */
+typedef struct {
+  int log;                  /* 0: plain (qNEI / qEI), 1: log (qLogNEI / qLogEI) */
+  double tau_relu;          /* log mode: fatplus temperature */
+  double tau_max;           /* log mode: fatmax temperature */
+  const double* best;       /* device: incumbent(s) in utility space */
+  int best_stride;          /* 1: S per-sample values, 0: one value */
+  int n_fac;                /* >= 0; 1 <= n_fac + n_add <= EVR_SOBO_MAX_TERMS */
+  const int* fac_out;       /* n_fac: model output index */
+  const int* fac_kind;      /* n_fac: EVR_OBJ_* */
+  const double* fac_w;      /* n_fac: exponent, finite and >= 1 */
+  const double* fac_p0;
+  const double* fac_p1;
+  const double* fac_p2;     /* read by EVR_OBJ_TARGET only */
+  int n_add;                /* >= 0 */
+  const int* add_out;
+  const int* add_kind;
+  const double* add_w;      /* n_add: weight in the bracket, finite */
+  const double* add_p0;
+  const double* add_p1;
+  const double* add_p2;
+} evr_mult;
+int evr_mult_scan(void* stream, int q, int m_model, int S, int b, const evr_mult* mt, const double* Y,
+                  const int* flags, const double* gout, double* acq, double* dY);
+/* Full evaluation: evr_qsobo_eval's chain (same stm / g / md / X / work / acq / dX semantics)
+ * with evr_mult_scan in place of evr_sobo_scan. */
+long long evr_qmult_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
+                                      const evr_qnehvi_model* md, int b, int backward);
+int evr_qmult_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
+                   const evr_mult* mt, int b, const double* X, const double* gout, double* work, double* acq,
+                   double* dX);
+
 /* ---- negative integrated posterior variance (ActiveLearningStrategy) --------------------
  * The per-candidate step of [upstream] qNegIntegratedPosteriorVariance as built by
  * bofire/strategies/predictives/active_learning.py:16-66 (restated from memory, parity-unpinned).
