@@ -42,6 +42,10 @@ class EvrQnehviModel(ctypes.Structure):
     _fields_ = [
         ("n", c_int), ("d", c_int), ("kind", c_int),
         ("Xn", c_void_p), ("lengthscales", c_void_p), ("shift", c_void_p), ("scale", c_void_p), ("M", c_void_p),
+        # mixed continuous / categorical model (all zero: the stationary model above)
+        ("mixed", c_int), ("dc", c_int), ("nc", c_int),
+        ("Xc", c_void_p), ("C", c_void_p), ("params", c_void_p),
+        ("cont_idx", c_void_p), ("cat_start", c_void_p), ("cat_len", c_void_p),
     ]
 
 
@@ -243,6 +247,9 @@ _SIGS = {
     "evr_nipv_reduce": ([c_void_p] + [c_int] * 7 + [c_void_p] * 2 + [c_int] + [c_void_p] * 13, c_int),
     "evr_mixed_kernel_matrix": ([c_void_p] + [c_int] * 6 + [c_void_p] * 7, c_int),
     "evr_mixed_kernel_param_grad": ([c_void_p] + [c_int] * 5 + [c_void_p] * 6, c_int),
+    "evr_mixed_split": ([c_void_p] + [c_int] * 4 + [c_void_p] * 8, c_int),
+    "evr_mixed_kernel_cross_grad_workspace_doubles": ([c_int, c_int, c_int], c_longlong),
+    "evr_mixed_kernel_cross_grad": ([c_void_p] + [c_int] * 7 + [c_void_p] * 10, c_int),
     "evr_objective_general": ([c_void_p, c_int, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 4, c_int),
     "evr_objective_weights": ([c_void_p, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 3, c_int),
     "evr_cells_kd_limits": ([c_int, c_int, c_int, c_void_p], c_int),

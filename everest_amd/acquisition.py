@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _native, ops
-from .gp import GPBatch
+from .gp import GPBatch, MixedGPBatch
 
 
 def sobol_base_samples(S: int, n_points: int, m: int, seed: int, device, scrambled=None) -> torch.Tensor:
@@ -108,6 +108,14 @@ def _host_threads() -> int:
         return max(1, int(v)) if v else min(16, os.cpu_count() or 1)
     except ValueError:
         return 1
+
+
+def _stationary_only(gp, name: str):
+    """The hypervolume chains, the op-by-op qEI and the integrated posterior variance read the
+    stationary model (Xn, lengthscales): a mixed model is refused, never read as one."""
+    if isinstance(gp, MixedGPBatch):
+        raise NotImplementedError(f"{name} does not run on a mixed (MixedSingleTaskGP) model; the single-objective "
+                                  "chain (QNEI, QLogNEI, QLogEI, QSobo*, QParego*, QMult*) does")
 
 
 def _single_cell(ref: torch.Tensor, S: int, m: int) -> ops.Cells:
@@ -554,6 +562,7 @@ class QNEHVI(_BoxHviAcqf):
                  num_threads: Optional[int] = None, box_device: Optional[bool] = None,
                  kd_scan: Optional[bool] = None, X_pending_raw: Optional[np.ndarray] = None,
                  root: Optional[str] = None, objective=None, constraints=(), alpha: float = 0.0):
+        _stationary_only(gp, type(self).__name__)
         dev = gp.device
         self.gp = gp
         self.dev = dev
@@ -860,6 +869,7 @@ class QEHVI(_BoxHviAcqf):
         """Y_part: points of the partition in objective space (m_obj columns); pending
         points ([upstream] concatenate_pending_points) join every candidate's joint batch;
         alpha > 0: [upstream] NondominatedPartitioning(alpha) instead of the exact partition."""
+        _stationary_only(gp, type(self).__name__)
         dev = gp.device
         self.gp, self.dev = gp, dev
         m, n = gp.B, gp.n
@@ -962,6 +972,7 @@ class QEIJoint(QEHVI):
 
     def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, obj_a: float, obj_b: float, S: int = 512,
                  seed: int = 0, X_pending_raw: Optional[np.ndarray] = None):
+        _stationary_only(gp, "QEIJoint")
         if gp.B != 1:
             raise ValueError("QEIJoint takes a single-output model")
         Xt = torch.as_tensor(np.asarray(X_train_raw, dtype=np.float64), device=gp.device)
@@ -1073,14 +1084,23 @@ class _NeiAcqf(_BoxHviAcqf):
         if X_pending_raw is not None and np.asarray(X_pending_raw).shape[0] > 0:
             self.X_pending = torch.as_tensor(np.asarray(X_pending_raw, dtype=np.float64).reshape(-1, gp.d), **f64)
         self.n_pending = 0 if self.X_pending is None else int(self.X_pending.shape[0])
-        self.Xk = gp.Xn
         self.Rr = gp.n + self.nb + (0 if no_h else self.S) + 1
         self.state = ops.model_state(gp.n, self.nb, self.S, gp.const, gp.ym, gp.ys, gp.kxx, no_h=no_h, m=m)
         self._lo_c = gp.lo.to(torch.float64).contiguous()
         self._scale_c = gp.inv_range.to(torch.float64).contiguous()
-        self.model = _native.EvrQnehviModel(n=gp.n, d=gp.d, kind=gp.kind, Xn=self.Xk.data_ptr(),
-                                            lengthscales=gp.ls.data_ptr(), shift=self._lo_c.data_ptr(),
-                                            scale=self._scale_c.data_ptr(), M=self.M.data_ptr())
+        if isinstance(gp, MixedGPBatch):
+            # the mixed model of the chain: candidates stay raw d-wide rows, split on the device
+            self.Xk = gp.Xc
+            self.model = _native.EvrQnehviModel(n=gp.n, d=gp.d, kind=gp.kind, shift=self._lo_c.data_ptr(),
+                                                scale=self._scale_c.data_ptr(), M=self.M.data_ptr(), mixed=1,
+                                                dc=gp.dc, nc=gp.nc, Xc=gp.Xc.data_ptr(), C=gp.C.data_ptr(),
+                                                params=gp.params.data_ptr(), cont_idx=gp.cont_idx.data_ptr(),
+                                                cat_start=gp.cat_start.data_ptr(), cat_len=gp.cat_len.data_ptr())
+        else:
+            self.Xk = gp.Xn
+            self.model = _native.EvrQnehviModel(n=gp.n, d=gp.d, kind=gp.kind, Xn=self.Xk.data_ptr(),
+                                                lengthscales=gp.ls.data_ptr(), shift=self._lo_c.data_ptr(),
+                                                scale=self._scale_c.data_ptr(), M=self.M.data_ptr())
         self.best = self.best.to(**f64).reshape(-1).contiguous()
         self.chain = self._chain_struct()
         self._zq_cache = {}
@@ -1637,6 +1657,7 @@ class QEI:
 
     def __init__(self, gp: GPBatch, X_train_raw: np.ndarray, obj_a: float, obj_b: float, S: int = 512,
                  seed: int = 0, z: Optional[torch.Tensor] = None):
+        _stationary_only(gp, "QEI")
         if gp.B != 1:
             raise ValueError("QEI takes a single-output model")
         self.gp = gp
@@ -1705,6 +1726,7 @@ class QNegIntPosVar:
     nonnegative = False     # values are <= 0: optimize_acqf takes initialize_q_batch ([upstream] is_nonnegative)
 
     def __init__(self, gp: GPBatch, P_raw, weights=None, X_pending_raw=None):
+        _stationary_only(gp, "QNegIntPosVar")
         if gp.mask is not None:
             raise NotImplementedError("QNegIntPosVar: outputs fitted on different row sets are not supported")
         self.gp = gp

@@ -52,6 +52,79 @@ struct QgDims {
   int n, nb, nh, S, m, b;
 };
 
+// mixed_chain.hip
+bool mixed_model_sizes_ok(int kind, int B, int dc, int nc);
+size_t mixed_kcross_grad_ws_doubles(int n, int rows, int dc);
+int mixed_kcross_grad_launch(hipStream_t s, int kind, int B, int n, int rows, int d, int dc, int nc, const double* Xc,
+                             const int* C, const double* X2c, const int* C2, const double* params,
+                             const double* scale, const int* cont_idx, const double* G, double* dX, double* work);
+int mixed_split_launch(hipStream_t s, int rows, int d, int dc, int nc, const double* X, const double* shift,
+                       const double* scale, const int* cont_idx, const int* cat_start, const int* cat_len, double* Xc,
+                       int* Cc);
+
+// The joint batch of a mixed model (evr_qnehvi_model.mixed) as the q x q Gram and its gradient
+// read it: the split candidates (rows c q + i), the members' parameters and the column map back
+// into the d-wide rows.  Unused (all zero) by the stationary instantiations.
+struct QgMixed {
+  int dc, nc;
+  const double* Xc;
+  const int* Cc;
+  const double* params;
+  const double* scale;
+  const int* cont_idx;
+};
+
+// Gradient factors of member j's mixed kernel at the pair (x_a, x_b):
+// dK / dxa_k = (u1 / ls1_k^2 + u2 / ls2_k^2) (xa_k - xb_k) in normalised units.
+__device__ __forceinline__ void qg_mixed_pair_grad(int kind, const QgMixed& mx, int j, size_t ra, size_t rb, double* u1,
+                                                   double* u2) {
+  const int dc = mx.dc, nc = mx.nc;
+  const double* pb = mx.params + (size_t)j * (2 * dc + 2 * nc + 3);
+  const double* xa = mx.Xc + ra * dc;
+  const double* xb = mx.Xc + rb * dc;
+  const int* ca = mx.Cc + ra * nc;
+  const int* cb = mx.Cc + rb * nc;
+  double q1 = 0.0, q2 = 0.0, e2 = 0.0;
+  for (int k = 0; k < dc; ++k) {
+    const double df = xa[k] - xb[k];
+    const double t1 = df / pb[k], t2 = df / pb[dc + k];
+    q1 = fma(t1, t1, q1);
+    q2 = fma(t2, t2, q2);
+  }
+  for (int f = 0; f < nc; ++f)
+    if (ca[f] != cb[f]) e2 += 1.0 / ((double)nc * pb[2 * dc + nc + f]);
+  *u1 = pb[2 * dc + 2 * nc] * kernel_dscale(kind, q1);
+  *u2 = pb[2 * dc + 2 * nc + 2] * exp_k(-e2) * kernel_dscale(kind, q2);
+}
+
+constexpr int QG_MX_MAXD = 32, QG_MX_MAXC = 8;   // the mixed kernel's limits (mixed_kernel.hip)
+
+// The member's vectors as the candidate Gram reads them, staged once per workgroup in LDS:
+// 1 / ls1, 1 / ls2 (dc each), 1 / (nc lam1), 1 / (nc lam2) (nc each), then s_sum, s_cat, s_prod.
+struct QgMixedLds {
+  double il1[QG_MX_MAXD], il2[QG_MX_MAXD], w1[QG_MX_MAXC], w2[QG_MX_MAXC], sc[3];
+};
+
+// K(x_a, x_b) of the member's mixed kernel (mixed_kmat_kernel's expression) from the staged
+// vectors.  Called once, by the thread that owns the pair (its index is a run-time value): inside
+// the unrolled Q (Q + 1) / 2 nest of thread 0 its copies spilled to scratch from Q = 6 on.
+__device__ __forceinline__ double qg_mixed_pair_value(int kind, int dc, int nc, const double* xa, const double* xb,
+                                                   const int* ca, const int* cb, const QgMixedLds* v) {
+  double q1 = 0.0, q2 = 0.0, e1 = 0.0, e2 = 0.0;
+  for (int k = 0; k < dc; ++k) {
+    const double df = xa[k] - xb[k];
+    const double t1 = df * v->il1[k], t2 = df * v->il2[k];
+    q1 = fma(t1, t1, q1);
+    q2 = fma(t2, t2, q2);
+  }
+  for (int f = 0; f < nc; ++f)
+    if (ca[f] != cb[f]) {
+      e1 += v->w1[f];
+      e2 += v->w2[f];
+    }
+  return fma(v->sc[2] * kernel_value(kind, q2), exp_k(-e2), v->sc[0] * fma(v->sc[1], exp_k(-e1), kernel_value(kind, q1)));
+}
+
 // fixed-order block sum over 256 threads (4 waves): xor-butterfly in the wave, then waves 0..3
 __device__ __forceinline__ double qg_block_sum(double v, double* red4) {
 #pragma unroll
@@ -69,7 +142,7 @@ __device__ __forceinline__ double qg_block_sum(double v, double* red4) {
 //   Sigma22[i][i'] = s^2 (k(x_i, x_i') - sum_{r<n} R_ri R_ri') - sum_{n<=r<n+nb} R_ri R_ri'
 // (rows < n: L^-1 k or the fused root C k; rows [n, n+nb): L21 = G k of the split layout).
 // ---------------------------------------------------------------------------------------
-template <int Q>
+template <int Q, bool MIXED = false>
 __global__ __launch_bounds__(256) void qg_gram_samples(QgDims dm, int kind, int d, const double* __restrict__ R,
                                                        const double* __restrict__ X, const double* __restrict__ ls,
                                                        const double* __restrict__ shift,
@@ -77,7 +150,8 @@ __global__ __launch_bounds__(256) void qg_gram_samples(QgDims dm, int kind, int 
                                                        const double* __restrict__ cc, const double* __restrict__ ym,
                                                        const double* __restrict__ ys, const double* __restrict__ kxx,
                                                        const double* __restrict__ zq, double* __restrict__ Y,
-                                                       double* __restrict__ Lq, int* __restrict__ flags) {
+                                                       double* __restrict__ Lq, int* __restrict__ flags,
+                                                       QgMixed mx) {
   constexpr int NP = Q * (Q + 1) / 2;
   __shared__ double red4[4];
   __shared__ double Ls[Q * Q];
@@ -105,8 +179,36 @@ __global__ __launch_bounds__(256) void qg_gram_samples(QgDims dm, int kind, int 
   double gram[NP];
 #pragma unroll
   for (int p = 0; p < NP; ++p) gram[p] = qg_block_sum(acc[p], red4);
+  // mixed model: the prior covariance of pair p = i (i + 1) / 2 + i2 by thread p, from the member's
+  // vectors staged in LDS; thread 0 then reads kq_s[p] in its unrolled nest
+  __shared__ double kq_s[MIXED ? NP : 1];
+  if constexpr (MIXED) {
+    __shared__ QgMixedLds mv;
+    const int dc = mx.dc, nc = mx.nc;
+    const double* pb = mx.params + (size_t)j * (2 * dc + 2 * nc + 3);
+    if (tid < dc) {
+      mv.il1[tid] = 1.0 / pb[tid];
+      mv.il2[tid] = 1.0 / pb[dc + tid];
+    }
+    if (tid >= 64 && tid < 64 + nc) {
+      const int f = tid - 64;
+      mv.w1[f] = 1.0 / ((double)nc * pb[2 * dc + f]);
+      mv.w2[f] = 1.0 / ((double)nc * pb[2 * dc + nc + f]);
+    }
+    if (tid >= 128 && tid < 131) mv.sc[tid - 128] = pb[2 * dc + 2 * nc + tid - 128];
+    __syncthreads();
+    if (tid < NP) {
+      int i = 0;
+      while ((i + 1) * (i + 2) / 2 <= tid) ++i;
+      const int i2 = tid - i * (i + 1) / 2;
+      const size_t ra = (size_t)c * Q + i, rb = (size_t)c * Q + i2;
+      kq_s[tid] = i2 == i ? kxx[j]
+                          : qg_mixed_pair_value(kind, dc, nc, mx.Xc + ra * dc, mx.Xc + rb * dc, mx.Cc + ra * nc,
+                                                mx.Cc + rb * nc, &mv);
+    }
+    __syncthreads();
+  }
   if (tid == 0) {
-    const double* lsj = ls + (size_t)j * d;
     double A[Q][Q];
     int p = 0;
 #pragma unroll
@@ -114,7 +216,10 @@ __global__ __launch_bounds__(256) void qg_gram_samples(QgDims dm, int kind, int 
 #pragma unroll
       for (int i2 = 0; i2 <= i; ++i2) {
         double kq = kxx[j];
-        if (i2 != i) {
+        if constexpr (MIXED) {
+          kq = kq_s[p];
+        } else if (i2 != i) {
+          const double* lsj = ls + (size_t)j * d;
           double d2 = 0.0;
           const double* xa = X + ((size_t)c * Q + i) * d;
           const double* xb = X + ((size_t)c * Q + i2) * d;
@@ -450,16 +555,38 @@ __global__ __launch_bounds__(256) void qg_gen_gr(QgDims dm, const double* __rest
 }
 
 // dX[c q + i] += sum_j sum_{i' != i} 2 dKqq[j][c][i][i'] dk_j(x_i, x_i')/dx_i (raw coordinates)
-template <int Q>
+template <int Q, bool MIXED = false>
 __global__ __launch_bounds__(64) void qg_kqq_grad(int b, int m, int d, int kind, const double* __restrict__ X,
                                                   const double* __restrict__ ls, const double* __restrict__ shift,
                                                   const double* __restrict__ scale, const double* __restrict__ kxx,
-                                                  const double* __restrict__ dKqq, double* __restrict__ dX) {
+                                                  const double* __restrict__ dKqq, double* __restrict__ dX,
+                                                  QgMixed mx) {
   const int col = blockIdx.x * 64 + threadIdx.x;
   if (col >= b * Q) return;
   const int c = col / Q, i = col - c * Q;
   const double* xa = X + (size_t)col * d;
   double* out = dX + (size_t)col * d;
+  if constexpr (MIXED) {
+    // the pair term over (Xc, Cc): continuous columns only, scattered with 1 / (hi - lo)
+    const double* xca = mx.Xc + (size_t)col * mx.dc;
+    for (int j = 0; j < m; ++j) {
+      const double* pb = mx.params + (size_t)j * (2 * mx.dc + 2 * mx.nc + 3);
+      for (int i2 = 0; i2 < Q; ++i2) {
+        if (i2 == i) continue;
+        const double coef = 2.0 * dKqq[((size_t)j * b + c) * Q * Q + i * Q + i2];
+        if (coef == 0.0) continue;
+        double u1, u2;
+        qg_mixed_pair_grad(kind, mx, j, (size_t)col, (size_t)c * Q + i2, &u1, &u2);
+        const double* xcb = mx.Xc + ((size_t)c * Q + i2) * mx.dc;
+        for (int k = 0; k < mx.dc; ++k) {
+          const int t = mx.cont_idx[k];
+          const double l1 = pb[k], l2 = pb[mx.dc + k], df = xca[k] - xcb[k];
+          out[t] += coef * (u1 * df / (l1 * l1) + u2 * df / (l2 * l2)) * mx.scale[t];
+        }
+      }
+    }
+    return;
+  }
   for (int j = 0; j < m; ++j) {
     const double* lsj = ls + (size_t)j * d;
     for (int i2 = 0; i2 < Q; ++i2) {
@@ -588,6 +715,7 @@ static QgLayout qg_layout(const evr_qnehvi_state* stm, const evr_qnehvi_state* s
 static int qg_check(const evr_qnehvi_state* stm, const evr_qnehvi_state* sth, const evr_qn_general* g,
                     const evr_qnehvi_model* md) {
   EVR_CHECK(stm && sth && g && md, "qnehvi_general: null argument");
+  EVR_CHECK(!md->mixed, "qnehvi_general: the hypervolume chains do not take a mixed (categorical-kernel) model");
   EVR_CHECK(g->q >= 1 && g->q <= EVR_QNG_MAX_Q, "qnehvi_general: q = %d outside 1..%d", g->q, EVR_QNG_MAX_Q);
   EVR_CHECK(sth->m == g->m_obj && sth->S == stm->S && !sth->log_hvi,
             "qnehvi_general: scan state must carry m = m_obj objectives, the same S, and log_hvi = 0");
@@ -1002,6 +1130,10 @@ extern "C" {
 long long evr_qng_workspace_doubles(const evr_qnehvi_state* stm, const evr_qnehvi_state* sth, const evr_qn_general* g,
                                     const evr_qnehvi_model* md, int b, int backward) {
   if (!stm || !sth || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q) return 0;
+  if (md->mixed) {   // the eval refuses a mixed model: no size to hand out for it
+    set_error("evr_qng_workspace_doubles: the hypervolume chains do not take a mixed (categorical-kernel) model");
+    return 0;
+  }
   return (long long)qg_layout(stm, sth, g->q, md->d, b, backward != 0).total;
 }
 
@@ -1035,7 +1167,8 @@ int evr_qng_eval(void* stream, const evr_qnehvi_state* stm, const evr_qnehvi_sta
   if (int rc = proj_forward(s, stm, bq, md->M, Kx, R, w + L.P, L.Wf != L.Y ? w + L.Wf : nullptr)) return rc;
 #define GO(QQ)                                                                                                   \
   qg_gram_samples<QQ><<<dim3(b, m), 256, 0, s>>>(dm, md->kind, d, R, X, md->lengthscales, md->shift, md->scale,   \
-                                                 stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags);       \
+                                                 stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags, \
+                                                 QgMixed{});      \
   EVR_LAUNCH_CHECK();                                                                                            \
   qg_subsets<QQ><<<dim3(cdiv(b, 64), S), 64, 0, s>>>(S, b, o, Y, Gv, Wv);                                         \
   EVR_LAUNCH_CHECK()
@@ -1072,7 +1205,7 @@ int evr_qng_eval(void* stream, const evr_qnehvi_state* stm, const evr_qnehvi_sta
   if (q > 1) {
 #define GO(QQ)                                                                                                   \
   qg_kqq_grad<QQ><<<cdiv(bq, 64), 64, 0, s>>>(b, m, d, md->kind, X, md->lengthscales, md->shift, md->scale,       \
-                                              stm->kxx, dKqq, dX);                                               \
+                                              stm->kxx, dKqq, dX, QgMixed{});                                             \
   EVR_LAUNCH_CHECK()
     QG_SWITCH(q, GO);
 #undef GO
@@ -1106,6 +1239,10 @@ int evr_objective_weights(void* stream, int m_model, int n, const evr_qn_general
 long long evr_qlog_workspace_doubles(const evr_qnehvi_state* stm, const evr_qnehvi_state* sth, const evr_qn_general* g,
                                      const evr_qnehvi_model* md, int b, int backward) {
   if (!stm || !sth || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q) return 0;
+  if (md->mixed) {   // the eval refuses a mixed model: no size to hand out for it
+    set_error("evr_qlog_workspace_doubles: the hypervolume chains do not take a mixed (categorical-kernel) model");
+    return 0;
+  }
   return (long long)ql_layout(stm, sth, g->q, md->d, b, backward != 0).total;
 }
 
@@ -1113,6 +1250,7 @@ int evr_qlog_eval(void* stream, const evr_qnehvi_state* stm, const evr_qnehvi_st
                   const evr_qnehvi_model* md, int b, const double* X, const double* gout, double* work, double* acq,
                   double* dX) {
   EVR_CHECK(stm && sth && g && md, "evr_qlog_eval: null argument");
+  EVR_CHECK(!md->mixed, "evr_qlog_eval: the hypervolume chains do not take a mixed (categorical-kernel) model");
   EVR_CHECK(g->q >= 1 && g->q <= EVR_QNG_MAX_Q, "evr_qlog_eval: q = %d outside 1..%d", g->q, EVR_QNG_MAX_Q);
   EVR_CHECK(sth->m == g->m_obj && sth->S == stm->S && sth->cell_lo && sth->cell_hi && sth->cell_off,
             "evr_qlog_eval: the scan state must carry m = m_obj objectives, the same S and explicit cells");
@@ -1145,7 +1283,8 @@ int evr_qlog_eval(void* stream, const evr_qnehvi_state* stm, const evr_qnehvi_st
   const dim3 grid(cdiv(b, P.CT), S, P.nsplit);
 #define GO(QQ)                                                                                                    \
   qg_gram_samples<QQ><<<dim3(b, m), 256, 0, s>>>(dm, md->kind, d, R, X, md->lengthscales, md->shift, md->scale,    \
-                                                 stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags);        \
+                                                 stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags, \
+                                                 QgMixed{});       \
   EVR_LAUNCH_CHECK();                                                                                             \
   if (L.MM == 4) {                                                                                                \
     if (backward) qlog_scan<4, QQ, true><<<grid, QL_THREADS, 0, s>>>(b, P.nsplit, P.CT, P.CB, o, Y, sth->cell_off,  \
@@ -1199,7 +1338,7 @@ int evr_qlog_eval(void* stream, const evr_qnehvi_state* stm, const evr_qnehvi_st
   if (q > 1) {
 #define GO(QQ)                                                                                                   \
   qg_kqq_grad<QQ><<<cdiv(bq, 64), 64, 0, s>>>(b, m, d, md->kind, X, md->lengthscales, md->shift, md->scale,       \
-                                              stm->kxx, dKqq, dX);                                               \
+                                              stm->kxx, dKqq, dX, QgMixed{});                                             \
   EVR_LAUNCH_CHECK()
     QG_SWITCH(q, GO);
 #undef GO
@@ -1231,14 +1370,16 @@ int mult_scan_launch(hipStream_t s, int q, int m_model, int S, int b, const evr_
                      const int* flags, const double* gout, double* acq, double* dY);
 
 struct QnLayout {
-  size_t Kx, R, P, Wf, Y, Lq, flags, dY, cf, dKqq, cm, gR, dKx, Wb, kg, total;
+  size_t Kx, R, P, Wf, Y, Lq, flags, Xc, Cc, dY, cf, dKqq, cm, gR, dKx, Wb, kg, total;
 };
 
-// m = stm->m model outputs (1 for evr_qnei_eval)
-static QnLayout qn_layout(const evr_qnehvi_state* stm, int q, int d, int b, bool backward) {
+// m = stm->m model outputs (1 for evr_qnei_eval).  A mixed model adds the split candidates
+// (Xc, Cc) and takes the mixed X-gradient's workspace for kg.
+static QnLayout qn_layout(const evr_qnehvi_state* stm, const evr_qnehvi_model* md, int q, int b, bool backward) {
   QnLayout L{};
   const size_t m = stm->m, n = stm->n, S = stm->S, bq = (size_t)b * q;
   const size_t Rr = (size_t)qn_rows(stm);
+  const bool mixed = md->mixed != 0;
   size_t o = 0;
   auto take = [&](size_t doubles) {
     const size_t r = o;
@@ -1252,6 +1393,10 @@ static QnLayout qn_layout(const evr_qnehvi_state* stm, int q, int d, int b, bool
   L.Y = take(S * m * bq);
   L.Lq = take(m * b * q * q);
   L.flags = take((m * b + 1) / 2);
+  if (mixed) {
+    L.Xc = take(bq * (size_t)md->dc);
+    L.Cc = take((bq * (size_t)md->nc + 1) / 2);
+  }
   if (backward) {
     L.dY = take(S * m * bq);
     L.cf = take(m * b * q * q);
@@ -1260,30 +1405,43 @@ static QnLayout qn_layout(const evr_qnehvi_state* stm, int q, int d, int b, bool
     L.gR = take(m * Rr * bq);
     L.dKx = take(m * n * bq);
     L.Wb = take(dg_gemm_ws_doubles(true, (int)n, (int)bq, (int)Rr, (int)m));
-    L.kg = take(kcross_grad_ws_doubles((int)n, (int)bq, d));
+    L.kg = take(mixed ? mixed_kcross_grad_ws_doubles((int)n, (int)bq, md->dc)
+                      : kcross_grad_ws_doubles((int)n, (int)bq, md->d));
   }
   L.total = o;
   return L;
 }
 
-// The chain the three entry points below share: kernel matrix -> projection -> q x q Gram /
+static bool qn_mixed_ok(const evr_qnehvi_model* md, int m) {
+  return mixed_model_sizes_ok(md->kind, m, md->dc, md->nc) && md->d >= md->dc + md->nc && md->Xc && md->C &&
+         md->params && md->shift && md->scale && md->cont_idx && md->cat_start && md->cat_len;
+}
+
+// The chain the entry points below share: kernel matrix -> projection -> q x q Gram /
 // jittered Cholesky / joint samples per (candidate, output) -> scan(Y, flags, dY) -> (dX != NULL)
 // analytic backward.  The entry points differ only in their checks and the scan they launch.
+// The model enters at four sites — K*, the candidate Gram, the cross-covariance X-gradient and
+// the Gram's pair gradient; a mixed model (md->mixed) splits the candidates first and takes the
+// mixed form at each of them, everything between is shared.
 template <class Scan>
 static int qn_chain(const char* who, hipStream_t s, const evr_qnehvi_state* stm, const evr_qn_general* g,
                     const evr_qnehvi_model* md, int b, const double* X, double* work, double* acq, double* dX,
                     Scan scan) {
   EVR_CHECK(g->q >= 1 && g->q <= EVR_QNG_MAX_Q, "%s: q = %d outside 1..%d", who, g->q, EVR_QNG_MAX_Q);
   EVR_CHECK(stm->m >= 1 && stm->m <= QG_MAXM, "%s: %d model outputs outside 1..%d", who, stm->m, QG_MAXM);
-  EVR_CHECK(md->n == stm->n && md->d >= 1 && md->M && md->Xn && md->lengthscales && g->zq && stm->c && stm->ym &&
-                stm->ys && stm->kxx && stm->S >= 1,
+  const bool mixed = md->mixed != 0;
+  EVR_CHECK(md->n == stm->n && md->d >= 1 && md->M && (mixed || (md->Xn && md->lengthscales)) && g->zq && stm->c &&
+                stm->ym && stm->ys && stm->kxx && stm->S >= 1,
             "%s: inconsistent model / state", who);
+  EVR_CHECK(!mixed || qn_mixed_ok(md, stm->m),
+            "%s: bad mixed model (kind=%d one family 0..3, d=%d, 1 <= dc=%d <= 32, 1 <= nc=%d <= 8, d >= dc + nc, "
+            "Xc / C / params / shift / scale / column maps set)", who, md->kind, md->d, md->dc, md->nc);
   EVR_CHECK(X && work && acq && b >= 0, "%s: bad arguments", who);
   if (b == 0) return 0;
   const int q = g->q, m = stm->m, n = stm->n, d = md->d, S = stm->S;
   const int bq = b * q;
   const bool backward = dX != nullptr;
-  const QnLayout L = qn_layout(stm, q, d, b, backward);
+  const QnLayout L = qn_layout(stm, md, q, b, backward);
   double* w = work;
   double* Kx = w + L.Kx;
   double* R = w + L.R;
@@ -1291,14 +1449,30 @@ static int qn_chain(const char* who, hipStream_t s, const evr_qnehvi_state* stm,
   double* Lq = w + L.Lq;
   int* flags = (int*)(w + L.flags);
   double* dY = backward ? w + L.dY : nullptr;
+  double* Xc = mixed ? w + L.Xc : nullptr;
+  int* Cc = mixed ? (int*)(w + L.Cc) : nullptr;
+  const QgMixed mx = mixed ? QgMixed{md->dc, md->nc, Xc, Cc, md->params, md->scale, md->cont_idx} : QgMixed{};
   const QgDims dm{n, stm->nb, qn_nh(stm), S, m, b};
-  if (int rc = evr_kernel_matrix(s, md->kind, m, n, bq, d, md->Xn, nullptr, nullptr, X, md->shift, md->scale,
-                                 md->lengthscales, nullptr, nullptr, Kx))
+  if (mixed) {
+    if (int rc = mixed_split_launch(s, bq, d, md->dc, md->nc, X, md->shift, md->scale, md->cont_idx, md->cat_start,
+                                    md->cat_len, Xc, Cc))
+      return rc;
+    if (int rc = evr_mixed_kernel_matrix(s, md->kind, m, n, bq, md->dc, md->nc, md->Xc, md->C, Xc, Cc, md->params,
+                                         nullptr, Kx))
+      return rc;
+  } else if (int rc = evr_kernel_matrix(s, md->kind, m, n, bq, d, md->Xn, nullptr, nullptr, X, md->shift, md->scale,
+                                        md->lengthscales, nullptr, nullptr, Kx))
     return rc;
   if (int rc = proj_forward(s, stm, bq, md->M, Kx, R, w + L.P, L.Wf != L.Y ? w + L.Wf : nullptr)) return rc;
 #define GO(QQ)                                                                                                   \
-  qg_gram_samples<QQ><<<dim3(b, m), 256, 0, s>>>(dm, md->kind, d, R, X, md->lengthscales, md->shift, md->scale,   \
-                                                 stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags);       \
+  if (mixed)                                                                                                     \
+    qg_gram_samples<QQ, true><<<dim3(b, m), 256, 0, s>>>(dm, md->kind, d, R, X, nullptr, md->shift, md->scale,    \
+                                                         stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags, \
+                                                         mx);                                                    \
+  else                                                                                                           \
+    qg_gram_samples<QQ><<<dim3(b, m), 256, 0, s>>>(dm, md->kind, d, R, X, md->lengthscales, md->shift, md->scale, \
+                                                   stm->c, stm->ym, stm->ys, stm->kxx, g->zq, Y, Lq, flags,       \
+                                                   QgMixed{});                                                   \
   EVR_LAUNCH_CHECK()
   QG_SWITCH(q, GO);
 #undef GO
@@ -1320,13 +1494,21 @@ static int qn_chain(const char* who, hipStream_t s, const evr_qnehvi_state* stm,
   if (int rc = dg_gemm(s, true, n, bq, Rr, 1.0, md->M, n, (long long)Rr * n, gR, bq, (long long)Rr * bq, 0.0, dKx, bq,
                        (long long)n * bq, m, w + L.Wb))
     return rc;
-  if (int rc = kcross_grad_launch(s, md->kind, m, n, bq, d, md->Xn, nullptr, nullptr, X, md->shift, md->scale,
-                                  md->lengthscales, nullptr, dKx, dX, w + L.kg))
+  if (mixed) {
+    if (int rc = mixed_kcross_grad_launch(s, md->kind, m, n, bq, d, md->dc, md->nc, md->Xc, md->C, Xc, Cc, md->params,
+                                          md->scale, md->cont_idx, dKx, dX, w + L.kg))
+      return rc;
+  } else if (int rc = kcross_grad_launch(s, md->kind, m, n, bq, d, md->Xn, nullptr, nullptr, X, md->shift, md->scale,
+                                         md->lengthscales, nullptr, dKx, dX, w + L.kg))
     return rc;
   if (q > 1) {
 #define GO(QQ)                                                                                                   \
-  qg_kqq_grad<QQ><<<cdiv(bq, 64), 64, 0, s>>>(b, m, d, md->kind, X, md->lengthscales, md->shift, md->scale,       \
-                                              stm->kxx, dKqq, dX);                                               \
+  if (mixed)                                                                                                     \
+    qg_kqq_grad<QQ, true><<<cdiv(bq, 64), 64, 0, s>>>(b, m, d, md->kind, X, nullptr, md->shift, md->scale,        \
+                                                      stm->kxx, dKqq, dX, mx);                                   \
+  else                                                                                                           \
+    qg_kqq_grad<QQ><<<cdiv(bq, 64), 64, 0, s>>>(b, m, d, md->kind, X, md->lengthscales, md->shift, md->scale,     \
+                                                stm->kxx, dKqq, dX, QgMixed{});                                  \
   EVR_LAUNCH_CHECK()
     QG_SWITCH(q, GO);
 #undef GO
@@ -1341,7 +1523,7 @@ extern "C" {
 long long evr_qnei_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
                                      const evr_qnehvi_model* md, int b, int backward) {
   if (!stm || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q || stm->m != 1) return 0;
-  return (long long)qn_layout(stm, g->q, md->d, b, backward != 0).total;
+  return (long long)qn_layout(stm, md, g->q, b, backward != 0).total;
 }
 
 int evr_qnei_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_general* g, const evr_qnehvi_model* md,
@@ -1365,7 +1547,7 @@ int evr_qnei_eval(void* stream, const evr_qnehvi_state* stm, const evr_qn_genera
 static long long qn_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,
                                       const evr_qnehvi_model* md, int b, int backward) {
   if (!stm || !g || !md || b <= 0 || g->q < 1 || g->q > EVR_QNG_MAX_Q || stm->m < 1 || stm->m > QG_MAXM) return 0;
-  return (long long)qn_layout(stm, g->q, md->d, b, backward != 0).total;
+  return (long long)qn_layout(stm, md, g->q, b, backward != 0).total;
 }
 
 long long evr_qsobo_workspace_doubles(const evr_qnehvi_state* stm, const evr_qn_general* g,

@@ -259,12 +259,17 @@ extern "C" {
 long long evr_qnehvi_plan_workspace_bytes(const evr_qnehvi_state* st, const evr_qnehvi_model* md, int b,
                                           int backward) {
   if (!st || !md || b <= 0) return 0;
+  if (md->mixed) {   // evr_qnehvi_plan_create refuses a mixed model: no size to hand out for it
+    set_error("evr_qnehvi_plan_workspace_bytes: the plan does not take a mixed (categorical-kernel) model");
+    return 0;
+  }
   return (long long)plan_layout(st, md, b, backward).bytes;
 }
 
 int evr_qnehvi_plan_create(void* stream, const evr_qnehvi_state* st, const evr_qnehvi_model* md, int b,
                            int backward, const double* X, void* work, double* acq, double* dX, int use_graph,
                            evr_qnehvi_plan** out) {
+  EVR_CHECK(!md || !md->mixed, "evr_qnehvi_plan_create: the plan does not take a mixed (categorical-kernel) model");
   EVR_CHECK(st && md && out && X && work && acq && b >= 1 && (!backward || dX) && md->M && md->Xn &&
                 md->lengthscales && md->n == st->n && md->d >= 1 && kind_code_ok(md->kind, st->m),
             "evr_qnehvi_plan_create: bad arguments");

@@ -648,6 +648,7 @@ long long evr_qnehvi_small_workspace_doubles(const evr_qnehvi_state* st, int b, 
 
 int evr_qnehvi_small_forward(void* stream, const evr_qnehvi_state* st, const evr_qnehvi_model* md, int b,
                              const double* Kx, double* R, double* P) {
+  EVR_CHECK(!md || !md->mixed, "evr_qnehvi_small_forward: no mixed (categorical-kernel) model");
   EVR_CHECK(st && md && Kx && R && P && qs_applies(st, b, md->d), "evr_qnehvi_small_forward: bad arguments");
   return qs_forward((hipStream_t)stream, st, md, b, Kx, R, P);
 }
@@ -661,6 +662,7 @@ int evr_qnehvi_small_samples(void* stream, const evr_qnehvi_state* st, int b, co
 int evr_qnehvi_small_backward(void* stream, const evr_qnehvi_state* st, const evr_qnehvi_model* md, int b,
                               const double* X, const double* R, const double* L22, const double* dG, double* dXp,
                               double* dX) {
+  EVR_CHECK(!md || !md->mixed, "evr_qnehvi_small_backward: no mixed (categorical-kernel) model");
   EVR_CHECK(st && md && X && R && L22 && dG && dXp && dX && qs_applies(st, b, md->d),
             "evr_qnehvi_small_backward: bad arguments");
   return qs_backward((hipStream_t)stream, st, md, b, X, R, L22, dG, dXp, dX, nullptr, nullptr, nullptr, nullptr,

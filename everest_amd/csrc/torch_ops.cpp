@@ -165,6 +165,7 @@ struct QnehviAcq : torch::CustomClassHolder {
     stm = from_bytes<evr_qnehvi_state>("QnehviAcq", stm_b, "model-side state");
     sth = from_bytes<evr_qnehvi_state>("QnehviAcq", sth_b, "scan-side state");
     md = from_bytes<evr_qnehvi_model>("QnehviAcq", md_b, "model");
+    TORCH_CHECK(!md.mixed, "QnehviAcq: the hypervolume chains do not take a mixed (categorical-kernel) model");
     TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1, "QnehviAcq: inconsistent model");
   }
 
@@ -324,8 +325,11 @@ struct ChainAcq : torch::CustomClassHolder {
       : cls(cls_), op(op_), keep(std::move(keep_)) {
     stm = from_bytes<evr_qnehvi_state>(cls, stm_b, "model-side state");
     md = from_bytes<evr_qnehvi_model>(cls, md_b, "model");
-    TORCH_CHECK(md.M && md.Xn && md.lengthscales && md.n == stm.n && md.d >= 1 && stm.m >= 1, cls,
-                ": inconsistent model");
+    // a mixed model (md.mixed) carries Xc / C / params in place of Xn / lengthscales; the chain
+    // checks the rest of it
+    TORCH_CHECK(md.M && (md.mixed ? (md.Xc && md.C && md.params) : (md.Xn && md.lengthscales)) && md.n == stm.n &&
+                    md.d >= 1 && stm.m >= 1,
+                cls, ": inconsistent model");
     best = dev64(best_, "best");
     TORCH_CHECK(best.numel() == 1 || (per_sample && best.numel() == stm.S), cls,
                 per_sample ? ": best needs 1 or S values" : ": best needs one value");

@@ -4,7 +4,7 @@ from .domain import (BaseModel, CategoricalInput, CloseToTargetObjective, Constr
                      MinimizeSigmoidObjective, MovingMaximizeSigmoidObjective, Outputs, TargetObjective)
 from .models import (ActiveLearningStrategy, AdditiveSoboStrategy, AnyActiveLearningAcquisitionFunction, AnyStrategy, BotorchSurrogates, CategoricalEncodingEnum, CategoricalMethodEnum,
                      DimensionalityScaledLogNormalPrior, GammaPrior, HammingDistanceKernel, LogNormalPrior, MaternKernel,
-                     MixedSingleTaskGPSurrogate, MultiplicativeAdditiveSoboStrategy, MultiplicativeSoboStrategy, NormalPrior,
+                     MIXED_MODEL_STRATEGIES, MixedSingleTaskGPSurrogate, MultiplicativeAdditiveSoboStrategy, MultiplicativeSoboStrategy, NormalPrior,
                      QehviStrategy, QnehviStrategy, QparegoStrategy, RandomStrategy, RBFKernel, ScalerEnum, SingleTaskGPSurrogate,
                      SoboStrategy, MoboStrategy, qEHVI, qEI, qLogEHVI, qLogEI, qLogNEHVI, qLogNEI, qNEHVI,
                      qNegIntPosVar, qNEI, qPI, qSR, qUCB)

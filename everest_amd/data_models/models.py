@@ -216,20 +216,29 @@ AnySurrogate = Annotated[Union[SingleTaskGPSurrogate], Field(discriminator="type
 
 
 class BotorchSurrogates(BaseModel):
+    """``surrogates`` holds the stationary specs and, as before, takes nothing else: a
+    MixedSingleTaskGPSurrogate there is a validation error.  Mixed specs travel in
+    ``mixed_surrogates`` (the reference keeps both kinds in ``surrogates``; a reference JSON with
+    mixed entries there does not load here)."""
     type: Literal["BotorchSurrogates"] = "BotorchSurrogates"
     surrogates: List[AnySurrogate] = Field(default_factory=list)
+    mixed_surrogates: List[MixedSingleTaskGPSurrogate] = Field(default_factory=list)
+
+    @property
+    def all_surrogates(self) -> list:
+        return list(self.surrogates) + list(self.mixed_surrogates)
 
     @property
     def input_preprocessing_specs(self):
         specs = {}
-        for s in self.surrogates:
+        for s in self.all_surrogates:
             specs.update(s.input_preprocessing_specs)
         return specs
 
     @property
     def outputs(self) -> Outputs:
         feats = []
-        for s in self.surrogates:
+        for s in self.all_surrogates:
             feats += list(s.outputs.features)
         return Outputs(features=feats)
 
@@ -367,25 +376,39 @@ class BotorchStrategy(Strategy):
 
     @model_validator(mode="after")
     def _surrogates(self):
-        """_generate_surrogate_specs: one default SingleTaskGPSurrogate per output without a
-        spec (bofire/data_models/strategies/predictives/botorch.py:195-239).  The reference
-        picks MixedSingleTaskGP when categorical inputs exist — out of scope here; such
-        domains need explicit SingleTaskGPSurrogate specs (one-hot inputs)."""
+        """_generate_surrogate_specs: one default surrogate per output without a spec
+        (bofire/data_models/strategies/predictives/botorch.py:195-239) — a SingleTaskGPSurrogate,
+        or, when the domain has categorical inputs, a MixedSingleTaskGPSurrogate as the reference
+        picks (held in ``surrogate_specs.mixed_surrogates``).  The mixed model runs inside the strategies of MIXED_MODEL_STRATEGIES only: the
+        others still need explicit SingleTaskGPSurrogate specs (one-hot inputs) for such a domain.
+        The FREE categorical method is not compatible with a mixed model (botorch.py:161-166)."""
         specs = self.surrogate_specs
         have = set(specs.outputs.get_keys())
-        new = list(specs.surrogates)
+        new, mixed = list(specs.surrogates), list(specs.mixed_surrogates)
         for key in sorted(set(self.domain.outputs.get_keys()) - have):
+            outputs = Outputs(features=[self.domain.outputs.get_by_key(key)])
             if len(self.domain.inputs.get(CategoricalInput, exact=True).features):
-                raise ValueError(f"output `{key}`: categorical inputs need an explicit SingleTaskGPSurrogate spec "
-                                 "(MixedSingleTaskGP is out of scope for the MI355X build)")
-            new.append(SingleTaskGPSurrogate(inputs=self.domain.inputs,
-                                             outputs=Outputs(features=[self.domain.outputs.get_by_key(key)])))
+                if type(self).__name__ not in MIXED_MODEL_STRATEGIES:
+                    raise ValueError(f"output `{key}`: categorical inputs need an explicit SingleTaskGPSurrogate "
+                                     f"spec (MixedSingleTaskGP is out of scope for {type(self).__name__} on the "
+                                     "MI355X build)")
+                mixed.append(MixedSingleTaskGPSurrogate(inputs=self.domain.inputs, outputs=outputs))
+            else:
+                new.append(SingleTaskGPSurrogate(inputs=self.domain.inputs, outputs=outputs))
         specs.__dict__["surrogates"] = new
-        for s in new:
+        specs.__dict__["mixed_surrogates"] = mixed
+        for s in new + mixed:
             for k in s.outputs.get_keys():
                 if k not in self.domain.outputs.get_keys():
                     raise KeyError(f"surrogate output `{k}` not in domain")
+        if self.categorical_method == CategoricalMethodEnum.FREE and mixed:
+            raise ValueError("Categorical method FREE not compatible with a a MixedSingleTaskGPModel.")
         return self
+
+
+# strategies whose acquisitions run on a MixedSingleTaskGPSurrogate (the single-objective chain)
+MIXED_MODEL_STRATEGIES = ("SoboStrategy", "AdditiveSoboStrategy", "MultiplicativeSoboStrategy",
+                          "MultiplicativeAdditiveSoboStrategy", "QparegoStrategy")
 
 
 _MO_CONSTRAINED = ("MaximizeObjective", "MinimizeObjective", "MinimizeSigmoidObjective", "MaximizeSigmoidObjective",

@@ -871,9 +871,14 @@ def fit_mixed(Xc: torch.Tensor, C: torch.Tensor, y_raw: np.ndarray, kind: int, l
 
 
 class MixedGPBatch:
-    """B mixed GPs (B = 1 is what the surrogate builds) on shared training inputs: Xc (n x dc,
-    normalised continuous columns, device) and C (n x nc int32 category codes, device).  Test
-    inputs are given the same way (the caller normalises and encodes)."""
+    """B mixed GPs on shared training inputs: Xc (n x dc, normalised continuous columns, device)
+    and C (n x nc int32 category codes, device).  Test inputs are given the same way (the caller
+    normalises and encodes) — or, once ``set_layout`` has described the transformed row, as raw
+    d-wide rows that are split on the device (ops.mixed_split): that is the form the
+    single-objective acquisitions read, beside the attributes they share with GPBatch (lo,
+    inv_range, d, kxx, M, ...; X_raw, output_keys and rows are set by compatibilize)."""
+
+    mask = None       # every member is trained on every row
 
     def __init__(self, Xc: torch.Tensor, C: torch.Tensor, Y: torch.Tensor, hypers: Sequence[MixedGPHyper], kind: int):
         self.Xc = Xc.contiguous()
@@ -894,7 +899,40 @@ class MixedGPBatch:
         self.kxx = t([mixed_kxx(h.params) for h in self.hypers])
         Yc = Y.to(device=dev, dtype=torch.float64).reshape(self.n, self.B).T.contiguous()
         self.y = ((Yc - self.ym[:, None]) / self.ys[:, None]).contiguous()
+        self.d = None
         self.refresh()
+
+    def set_layout(self, lo, hi, cont_cols, cat_blocks) -> "MixedGPBatch":
+        """Describe the transformed d-wide row: lo / hi (d) the Normalize bounds, cont_cols (dc)
+        the columns of the continuous inputs in Xc's order, cat_blocks (nc arrays) the contiguous
+        one-hot block of each categorical feature in C's order.  Returns self."""
+        dev = self.device
+        lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+        hi = np.asarray(hi, dtype=np.float64).reshape(-1)
+        d = lo.shape[0]
+        cont = np.asarray(cont_cols, dtype=np.int64).reshape(-1)
+        blocks = [np.asarray(b, dtype=np.int64).reshape(-1) for b in cat_blocks]
+        if cont.shape[0] != self.dc or len(blocks) != self.nc:
+            raise ValueError(f"layout of {cont.shape[0]} continuous columns / {len(blocks)} blocks for a model of "
+                             f"{self.dc} / {self.nc}")
+        for blk in blocks:
+            if blk.size < 1 or not np.array_equal(blk, np.arange(blk[0], blk[0] + blk.size)):
+                raise ValueError("every one-hot block must be a contiguous range of columns")
+        cols = np.concatenate([cont] + blocks)
+        if hi.shape[0] != d or cols.min() < 0 or cols.max() >= d or np.unique(cols).size != cols.size:
+            raise ValueError(f"column map does not fit rows of {d} columns")
+        self.d = int(d)
+        self.lo = torch.as_tensor(lo, device=dev)
+        self.hi = torch.as_tensor(hi, device=dev)
+        # one-hot columns are not normalised (their entries only decide the arg-max)
+        ir = np.ones(d)
+        ir[cont] = 1.0 / (hi[cont] - lo[cont])
+        self.inv_range = torch.as_tensor(ir, device=dev)
+        i32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.int32), device=dev)  # noqa: E731
+        self.cont_idx = i32(cont)
+        self.cat_start = i32([b[0] for b in blocks])
+        self.cat_len = i32([b.size for b in blocks])
+        return self
 
     # -- caches: L = chol(K + s2 I), Linv, alpha, M = [Linv; alpha^T] ----------------------
     def refresh(self):
@@ -905,14 +943,29 @@ class MixedGPBatch:
         self.alpha = ops.gemm(self.Linv, v, transA=True)[..., 0].contiguous()  # B x n
         self.M = torch.cat([self.Linv, self.alpha.unsqueeze(1)], dim=1).contiguous()  # B x (n+1) x n
 
-    def cross(self, Xc: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
-        """K(train, test): B x n x nt."""
+    def kernel_train(self, noise: bool = False) -> torch.Tensor:
+        return ops.mixed_kernel_matrix(self.Xc, self.C, self.Xc, self.C, self.params, self.kind,
+                                       diag_add=self.noise if noise else None)
+
+    def split(self, Xraw: torch.Tensor):
+        """(Xc, C) of raw transformed rows (rows x d), on the device (ops.mixed_split)."""
+        if self.d is None:
+            raise ValueError("MixedGPBatch: raw rows need set_layout first")
+        return ops.mixed_split(Xraw, self.lo, self.inv_range, self.cont_idx, self.cat_start, self.cat_len)
+
+    def cross(self, Xc: torch.Tensor, C: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """K(train, test): B x n x nt; test points as (Xc, C), or raw rows alone."""
+        if C is None:
+            Xc, C = self.split(Xc)
         return ops.mixed_kernel_matrix(self.Xc, self.C, Xc, C, self.params, self.kind)
 
-    def posterior(self, Xc: torch.Tensor, C: torch.Tensor, observation_noise: bool = False):
-        """Mean and variance (B x nt) at normalised continuous columns Xc and category codes C:
+    def posterior(self, Xc: torch.Tensor, C: Optional[torch.Tensor] = None, observation_noise: bool = False):
+        """Mean and variance (B x nt) at normalised continuous columns Xc and category codes C — or,
+        with C omitted, at raw transformed rows (split on the device):
         K_* = cross, R = M K_*, then the posterior finalize with k(x, x) = s_sum (1 + s_cat) + s_prod."""
         Xc = Xc.to(device=self.device, dtype=torch.float64).contiguous()
+        if C is None:
+            Xc, C = self.split(Xc)
         C = C.to(device=self.device, dtype=torch.int32).contiguous()
         R = ops.gemm(self.M, self.cross(Xc, C))
         return ops.posterior_finalize(R, self.const, self.ym, self.ys, self.kxx,

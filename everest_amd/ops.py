@@ -208,6 +208,58 @@ def mixed_kernel_param_grad(Xc, C, params, W, kind: int = 3) -> torch.Tensor:
     return g
 
 
+def _i32(t, name: str) -> torch.Tensor:
+    t = _dev(t, name, torch.int32)
+    if t.dim() != 1:
+        raise ValueError(f"{name} must be a vector, got {tuple(t.shape)}")
+    return t
+
+
+def mixed_split(X, shift, scale, cont_idx, cat_start, cat_len):
+    """(Xc rows x dc, Cc rows x nc int32) of raw transformed rows X (rows x d; evr_mixed_split):
+    Xc[:, k] = (X[:, cont_idx[k]] - shift[cont_idx[k]]) * scale[cont_idx[k]] and, per one-hot block
+    [cat_start[f], cat_start[f] + cat_len[f]), the arg-max, the first on ties.  shift / scale: d-wide."""
+    X, shift, scale = _dev(X, "mixed_split: X"), _dev(shift, "mixed_split: shift"), _dev(scale, "mixed_split: scale")
+    ci, cs, cl = (_i32(cont_idx, "mixed_split: cont_idx"), _i32(cat_start, "mixed_split: cat_start"),
+                  _i32(cat_len, "mixed_split: cat_len"))
+    if X.dim() != 2 or shift.numel() != X.shape[1] or scale.numel() != X.shape[1] or cs.numel() != cl.numel():
+        raise ValueError(f"mixed_split: X {tuple(X.shape)} must be rows x d with d-wide shift / scale and one "
+                         "start and length per block")
+    rows, d = X.shape
+    dc, nc = ci.numel(), cs.numel()
+    Xc = torch.empty(rows, dc, dtype=torch.float64, device=X.device)
+    Cc = torch.empty(rows, nc, dtype=torch.int32, device=X.device)
+    _mixed_call("evr_mixed_split", dc, nc, _stream(), rows, d, dc, nc, X.data_ptr(), shift.data_ptr(),
+                scale.data_ptr(), ci.data_ptr(), cs.data_ptr(), cl.data_ptr(), Xc.data_ptr(), Cc.data_ptr())
+    return Xc, Cc
+
+
+def mixed_kernel_cross_grad(Xc, C, X2c, C2, params, G, scale, cont_idx, kind: int = 3) -> torch.Tensor:
+    """dX (rows x d) of the mixed cross-covariance K(train, candidates) given G = dK (B x n x rows):
+    the continuous columns' gradient scattered to cont_idx with the factor scale (d-wide, 1 / (hi -
+    lo)), every other column exactly 0 (evr_mixed_kernel_cross_grad).  Bitwise reproducible."""
+    Xc, C, params, dc, nc = _mixed_args(Xc, C, params, "mixed_kernel_cross_grad")
+    X2c, C2 = _dev(X2c, "mixed_kernel_cross_grad: X2c"), _dev(C2, "mixed_kernel_cross_grad: C2", torch.int32)
+    G, scale = _dev(G, "G"), _dev(scale, "mixed_kernel_cross_grad: scale")
+    ci = _i32(cont_idx, "mixed_kernel_cross_grad: cont_idx")
+    B, n, rows, d = params.shape[0], Xc.shape[0], X2c.shape[0], scale.numel()
+    if (X2c.dim() != 2 or X2c.shape[1] != dc or tuple(C2.shape) != (rows, nc) or tuple(G.shape) != (B, n, rows)
+            or ci.numel() != dc):
+        raise ValueError(f"mixed_kernel_cross_grad: X2c {tuple(X2c.shape)} / C2 {tuple(C2.shape)} / G "
+                         f"{tuple(G.shape)} / cont_idx ({ci.numel()}) do not match B = {B}, n = {n}, dc = {dc}, "
+                         f"nc = {nc}")
+    # cont_idx is not read back here (no host sync per call): the reduction only matches column
+    # numbers against it, so an index outside the row selects nothing; MixedGPBatch.set_layout
+    # validates the map once, on the host
+    dX = torch.empty(rows, d, dtype=torch.float64, device=Xc.device)
+    lib = _native.load()
+    work = _workspace(lib.evr_mixed_kernel_cross_grad_workspace_doubles(n, rows, dc), Xc.device)
+    _mixed_call("evr_mixed_kernel_cross_grad", dc, nc, _stream(), int(kind), B, n, rows, d, dc, nc, Xc.data_ptr(),
+                C.data_ptr(), X2c.data_ptr(), C2.data_ptr(), params.data_ptr(), scale.data_ptr(), ci.data_ptr(),
+                G.data_ptr(), dX.data_ptr(), work.data_ptr())
+    return dX
+
+
 def mll_terms(L, Linv, r, alpha) -> torch.Tensor:
     """B x 5: logdet, quad, tr(K^-1), sum(alpha), sum(alpha^2)."""
     L, Linv, r, alpha = _dev(L, "L"), _dev(Linv, "Linv"), _dev(r, "r"), _dev(alpha, "alpha")

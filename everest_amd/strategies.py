@@ -27,6 +27,7 @@ from .acquisition import (QNegIntPosVar, QEHVI, QEI, QEIJoint, QLogEHVI, QLogEI,
 from .data_models.domain import CloseToTargetObjective, MaximizeObjective, MinimizeObjective
 from .optim import (OptimizeStats, hit_and_run, host_values, optimize_acqf, optimize_acqf_mixed,
                     prefetch_raw_samples)
+from .gp import MixedGPBatch
 from .surrogates import BotorchSurrogates, device
 
 
@@ -276,6 +277,11 @@ class BotorchStrategy(PredictiveStrategy):
         self.maxiter = data_model.maxiter
         self.batch_limit = data_model.batch_limit
         self.surrogate_specs = data_model.surrogate_specs
+        if (type(data_model).__name__ not in dm.MIXED_MODEL_STRATEGIES
+                and self.surrogate_specs.mixed_surrogates):
+            raise NotImplementedError(f"{type(data_model).__name__} does not run on MixedSingleTaskGPSurrogate specs: "
+                                      "the mixed model is built into the single-objective chain only ("
+                                      + ", ".join(dm.MIXED_MODEL_STRATEGIES) + ")")
         self.categorical_method = getattr(data_model.categorical_method, "value", data_model.categorical_method)
         self.surrogates: Optional[BotorchSurrogates] = None
         self.model = None
@@ -905,8 +911,11 @@ class SoboStrategy(BotorchStrategy):
         m = len(self.model.output_keys)
         if isinstance(af, (dm.qSR, dm.qUCB, dm.qPI)):
             return self._get_reward_acqfs(af, ops.SoboSpec(m, terms, constraints), X_train, X_pending, S)
-        if not (m == 1 and not constraints and len(terms) == 1 and terms[0][1] == ops.OBJ_AFFINE
-                and terms[0][2] == 1.0):
+        # qEI on a mixed model: QSoboLogEI(log=False), the general chain (QEI / QEIJoint read the
+        # stationary model op by op)
+        mixed_qei = isinstance(af, dm.qEI) and isinstance(self.model, MixedGPBatch)
+        if mixed_qei or not (m == 1 and not constraints and len(terms) == 1 and terms[0][1] == ops.OBJ_AFFINE
+                             and terms[0][2] == 1.0):
             return self._get_general_acqfs(af, ops.SoboSpec(m, terms, constraints), X_train, X_pending, S)
         a, b = terms[0][3], terms[0][4]
         if isinstance(af, (dm.qNEI, dm.qLogNEI)):

@@ -492,9 +492,10 @@ class MixedSingleTaskGPSurrogate:
         s = self.state
         dev = device()
         Xc, C = self.split_inputs(s["X"], s["lo"], s["hi"])
-        return MixedGPBatch(torch.as_tensor(Xc, device=dev), torch.as_tensor(C, device=dev),
-                            torch.as_tensor(s["y"][:, None], dtype=torch.float64, device=dev), [self.hyper()],
-                            s["kind"])
+        gp = MixedGPBatch(torch.as_tensor(Xc, device=dev), torch.as_tensor(C, device=dev),
+                          torch.as_tensor(s["y"][:, None], dtype=torch.float64, device=dev), [self.hyper()],
+                          s["kind"])
+        return gp.set_layout(s["lo"], s["hi"], self._cont_cols, self._cat_blocks)
 
     # ---- predict ----------------------------------------------------------------------
     def predict(self, experiments: pd.DataFrame) -> pd.DataFrame:
@@ -551,7 +552,7 @@ class BotorchSurrogates:
     """bofire/surrogates/botorch_surrogates.py:19-128."""
 
     def __init__(self, data_model: dm.BotorchSurrogates):
-        self.surrogates = [SingleTaskGPSurrogate(s) for s in data_model.surrogates]
+        self.surrogates = [map(s) for s in data_model.all_surrogates]
 
     def fit(self, experiments: pd.DataFrame):
         """Fits the per-output GPs (independent problems, as in the reference's sequential
@@ -565,7 +566,13 @@ class BotorchSurrogates:
 
         from .gp import fit_batch
 
-        rest = list(self.surrogates)
+        # mixed members: one after another (their MLL runs op by op, there is no lock-step plan)
+        for s in self.surrogates:
+            if isinstance(s, MixedSingleTaskGPSurrogate):
+                s.fit(experiments)
+        rest = [s for s in self.surrogates if not isinstance(s, MixedSingleTaskGPSurrogate)]
+        if not rest:
+            return
         if os.environ.get("EVR_FIT_BATCH", "1") != "0" and len(rest) > 1 and torch.cuda.is_available():
             probs = [(s, s._fit_problem(*s._fit_data(experiments))) for s in rest]
             groups = {}
@@ -620,6 +627,12 @@ class BotorchSurrogates:
         for k, s in zip(order, ss):
             if not s.is_fitted:
                 raise ValueError(f"Surrogate for output feature {k} not fitted.")
+        n_mixed = sum(isinstance(s, MixedSingleTaskGPSurrogate) for s in ss)
+        if n_mixed == len(ss):
+            return self._compatibilize_mixed(order, ss, inputs)
+        if n_mixed:
+            raise NotImplementedError("MixedSingleTaskGPSurrogate and SingleTaskGPSurrogate specs together: one "
+                                      "device model holds either mixed or stationary members, not both")
         d = ss[0].state["X"].shape[1]
         if any(s.state["X"].shape[1] != d for s in ss):
             raise NotImplementedError("surrogates over different input subsets are out of scope for the MI355X build")
@@ -646,6 +659,49 @@ class BotorchSurrogates:
         gp.output_keys = order
         gp.X_raw = X_all
         gp.rows = rows
+        return gp
+
+    @staticmethod
+    def _compatibilize_mixed(order, ss, inputs):
+        """Every surrogate mixed: one gp.MixedGPBatch of B members.  The members share their inputs
+        (Xc, C), so they must have been trained on the same rows, with the same continuous kernel
+        family and the same Normalize bounds — and over the strategy's own inputs: the chain splits
+        candidate rows of ``inputs``' transformed layout with the members' column map."""
+        from .gp import MixedGPBatch
+
+        s0 = ss[0]
+        st0 = s0.state
+        for s in ss:
+            own, _ = s.inputs._transform_info(s.input_preprocessing_specs)
+            dom, _ = inputs._transform_info(s.input_preprocessing_specs)
+            if (list(s.inputs.get_keys()) != list(inputs.get_keys())
+                    or any(list(own[k]) != list(dom[k]) for k in inputs.get_keys())):
+                raise NotImplementedError("a mixed surrogate over a subset or another order of the domain's inputs "
+                                          "is not supported: candidate rows are split with the surrogate's column "
+                                          "map")
+        for s in ss[1:]:
+            st = s.state
+            if st["X"].shape != st0["X"].shape or not np.array_equal(st["X"], st0["X"]):
+                raise NotImplementedError("mixed surrogates trained on different row sets are not supported (the "
+                                          "members of the mixed device model share their training inputs)")
+            if st["kind"] != st0["kind"]:
+                raise NotImplementedError("mixed surrogates with different continuous kernel families are not "
+                                          "supported in one device model")
+            if not (np.array_equal(st["lo"], st0["lo"]) and np.array_equal(st["hi"], st0["hi"])
+                    and np.array_equal(s._cont_cols, s0._cont_cols)
+                    and len(s._cat_blocks) == len(s0._cat_blocks)
+                    and all(np.array_equal(a, b) for a, b in zip(s._cat_blocks, s0._cat_blocks))):
+                raise NotImplementedError("mixed surrogates with different Normalize bounds or input layouts are "
+                                          "not supported in one device model")
+        dev = device()
+        Xc, C = s0.split_inputs(st0["X"], st0["lo"], st0["hi"])
+        Y = np.stack([s.state["y"] for s in ss], 1)
+        gp = MixedGPBatch(torch.as_tensor(Xc, device=dev), torch.as_tensor(C, device=dev),
+                          torch.as_tensor(Y, dtype=torch.float64, device=dev), [s.hyper() for s in ss], st0["kind"])
+        gp.set_layout(st0["lo"], st0["hi"], s0._cont_cols, s0._cat_blocks)
+        gp.output_keys = order
+        gp.X_raw = np.asarray(st0["X"], dtype=np.float64)
+        gp.rows = [np.arange(gp.n) for _ in ss]
         return gp
 
 

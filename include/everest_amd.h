@@ -95,6 +95,28 @@ int evr_mixed_kernel_matrix(void* stream, int kind, int B, int n1, int n2, int d
  * dc <= 8 and dc <= 16), a workgroup per row above. */
 int evr_mixed_kernel_param_grad(void* stream, int kind, int B, int n, int dc, int nc, const double* Xc, const int* C,
                                 const double* params, const double* W, double* g, double* work);
+/* Candidate split: raw transformed rows X (rows x d, continuous columns and one-hot blocks) ->
+ * Xc (rows x dc) = (X[:, cont_idx[k]] - shift[cont_idx[k]]) * scale[cont_idx[k]] (shift / scale
+ * d-wide, the Normalize bounds; exactly that subtraction and product) and Cc (rows x nc, int32):
+ * per block [cat_start[f], cat_start[f] + cat_len[f]) the arg-max, the first on ties
+ * ([upstream] OneHotToNumeric).  cont_idx / cat_start / cat_len: device int arrays. */
+int evr_mixed_split(void* stream, int rows, int d, int dc, int nc, const double* X, const double* shift,
+                    const double* scale, const int* cont_idx, const int* cat_start, const int* cat_len,
+                    double* Xc, int* Cc);
+/* X-gradient of the mixed cross-covariance K(train, candidates): given G = dK (B x n x rows),
+ *   dXc[j][k] = sum_b sum_i G[b][i][j] (s_sum k_c'(r1^2) (xc_jk - xc_ik) / ls1_k^2
+ *                                      + s_prod h2(i, j) k_c'(r2^2) (xc_jk - xc_ik) / ls2_k^2)
+ * (k_c' the families' derivative factor with the d2 < 1e-30 convention; the s_sum s_cat h1 term
+ * does not depend on x), written into the d-wide dX (rows x d) as dX[j][cont_idx[k]] =
+ * dXc[j][k] * scale[cont_idx[k]]; every other column (the one-hot blocks: the arg-max has no
+ * gradient) is set to exactly 0.  A row split into partials and a fixed-order reduction: no
+ * atomics, bitwise reproducible.  work: evr_mixed_kernel_cross_grad_workspace_doubles(n, rows,
+ * dc) doubles (NULL = allocate).  Instantiations for dc <= 8, <= 16, <= 32. */
+long long evr_mixed_kernel_cross_grad_workspace_doubles(int n, int rows, int dc);
+int evr_mixed_kernel_cross_grad(void* stream, int kind, int B, int n, int rows, int d, int dc, int nc,
+                                const double* Xc, const int* C, const double* X2c, const int* C2,
+                                const double* params, const double* scale, const int* cont_idx, const double* G,
+                                double* dX, double* work);
 
 /* Native MLL plan for the GP fit: B exact GPs sharing the normalised inputs Xn (n x d,
  * device, must outlive the plan) with standardised targets Y (B x n, device, copied).  One
@@ -352,6 +374,19 @@ typedef struct {
   const double* shift;         /* d: Normalize lower bounds (candidates arrive raw) */
   const double* scale;         /* d: 1 / (upper - lower) */
   const double* M;             /* m x (n + nb + S + 1) x n forward operator [Linv; G; H^T; alpha^T] */
+  /* Mixed continuous / categorical model (evr_mixed_kernel_matrix's kernel); all zero = the
+   * stationary model above.  With mixed != 0, Xn and lengthscales are not read; candidates still
+   * arrive as raw d-wide rows (one-hot blocks for the categoricals) and are split on the device
+   * (evr_mixed_split).  Only the chains of evr_qnei_eval / evr_qsobo_eval / evr_qparego_eval /
+   * evr_qreward_eval / evr_qmult_eval take a mixed model; every other entry point that reads
+   * this struct fails with an evr_last_error. */
+  int mixed, dc, nc;           /* flag, continuous columns (1..32), categorical features (1..8) */
+  const double* Xc;            /* n x dc normalised continuous training columns */
+  const int* C;                /* n x nc training category codes */
+  const double* params;        /* m x (2 dc + 2 nc + 3): [ls1 | ls2 | lam1 | lam2 | s_sum | s_cat | s_prod] */
+  const int* cont_idx;         /* dc: column of X holding continuous column k */
+  const int* cat_start;        /* nc: first column of categorical feature f's one-hot block */
+  const int* cat_len;          /* nc: levels (columns) of that block */
 } evr_qnehvi_model;
 typedef struct evr_qnehvi_plan evr_qnehvi_plan;
 long long evr_qnehvi_plan_workspace_bytes(const evr_qnehvi_state* st, const evr_qnehvi_model* md, int b,
