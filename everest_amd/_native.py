@@ -250,6 +250,10 @@ _SIGS = {
     "evr_mixed_split": ([c_void_p] + [c_int] * 4 + [c_void_p] * 8, c_int),
     "evr_mixed_kernel_cross_grad_workspace_doubles": ([c_int, c_int, c_int], c_longlong),
     "evr_mixed_kernel_cross_grad": ([c_void_p] + [c_int] * 7 + [c_void_p] * 10, c_int),
+    "evr_dot_kernel_apply": ([c_void_p] + [c_int] * 4 + [c_void_p] * 4, c_int),
+    "evr_dot_kernel_theta_grad": ([c_void_p] + [c_int] * 3 + [c_void_p] * 5, c_int),
+    "evr_dot_gp_posterior_workspace_doubles": ([c_int] * 4, c_longlong),
+    "evr_dot_gp_posterior": ([c_void_p] + [c_int] * 5 + [c_void_p] * 13, c_int),
     "evr_objective_general": ([c_void_p, c_int, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 4, c_int),
     "evr_objective_weights": ([c_void_p, c_int, c_int, POINTER(EvrQnGeneral)] + [c_void_p] * 3, c_int),
     "evr_cells_kd_limits": ([c_int, c_int, c_int, c_void_p], c_int),

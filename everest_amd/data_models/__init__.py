@@ -3,7 +3,8 @@ from .domain import (BaseModel, CategoricalInput, CloseToTargetObjective, Constr
                      LinearInequalityConstraint, MaximizeObjective, MaximizeSigmoidObjective, MinimizeObjective,
                      MinimizeSigmoidObjective, MovingMaximizeSigmoidObjective, Outputs, TargetObjective)
 from .models import (ActiveLearningStrategy, AdditiveSoboStrategy, AnyActiveLearningAcquisitionFunction, AnyStrategy, BotorchSurrogates, CategoricalEncodingEnum, CategoricalMethodEnum,
-                     DimensionalityScaledLogNormalPrior, GammaPrior, HammingDistanceKernel, LogNormalPrior, MaternKernel,
+                     DimensionalityScaledLogNormalPrior, GammaPrior, HammingDistanceKernel, LinearKernel, LinearSurrogate,
+                     LogNormalPrior, MaternKernel, PolynomialKernel, PolynomialSurrogate,
                      MIXED_MODEL_STRATEGIES, MixedSingleTaskGPSurrogate, MultiplicativeAdditiveSoboStrategy, MultiplicativeSoboStrategy, NormalPrior,
                      QehviStrategy, QnehviStrategy, QparegoStrategy, RandomStrategy, RBFKernel, ScalerEnum, SingleTaskGPSurrogate,
                      SoboStrategy, MoboStrategy, qEHVI, qEI, qLogEHVI, qLogEI, qLogNEHVI, qLogNEI, qNEHVI,

@@ -117,6 +117,23 @@ class MaternKernel(BaseModel):
 AnyKernel = Annotated[Union[RBFKernel, MaternKernel], Field(discriminator="type")]
 
 
+class LinearKernel(BaseModel):
+    """bofire/data_models/kernels/continuous.py:32-34.  Not part of AnyKernel: it is the kernel of
+    LinearSurrogate only."""
+    type: Literal["LinearKernel"] = "LinearKernel"
+    features: Optional[List[str]] = None
+    variance_prior: Optional[AnyPrior] = None
+
+
+class PolynomialKernel(BaseModel):
+    """bofire/data_models/kernels/continuous.py:37-40.  Not part of AnyKernel: it is the kernel of
+    PolynomialSurrogate only."""
+    type: Literal["PolynomialKernel"] = "PolynomialKernel"
+    features: Optional[List[str]] = None
+    offset_prior: Optional[AnyPrior] = None
+    power: int = 2
+
+
 class HammingDistanceKernel(BaseModel):
     """bofire/data_models/kernels/categorical.py:10-12."""
     type: Literal["HammingDistanceKernel"] = "HammingDistanceKernel"
@@ -210,6 +227,76 @@ class MixedSingleTaskGPSurrogate(BaseModel):
         if not isinstance(self.outputs.features[0], ContinuousOutput):
             raise ValueError("MixedSingleTaskGPSurrogate takes a continuous output")
         return self
+
+
+class LinearSurrogate(BaseModel):
+    """bofire/data_models/surrogates/linear.py:13-18 (without the hyperconfig and aggregations): an
+    exact GP with a LinearKernel.  Not part of AnySurrogate: it does not enter strategies."""
+    type: Literal["LinearSurrogate"] = "LinearSurrogate"
+    inputs: Inputs
+    outputs: Outputs
+    input_preprocessing_specs: Dict[str, CategoricalEncodingEnum] = Field(default_factory=dict, validate_default=True)
+    dump: Optional[str] = None
+    scaler: ScalerEnum = ScalerEnum.NORMALIZE
+    output_scaler: ScalerEnum = ScalerEnum.STANDARDIZE
+    kernel: LinearKernel = Field(default_factory=lambda: LinearKernel())
+    noise_prior: AnyPrior = Field(default_factory=lambda: THREESIX_NOISE_PRIOR())
+
+    @field_validator("output_scaler")
+    @classmethod
+    def _os(cls, v):
+        if v == ScalerEnum.NORMALIZE:
+            raise ValueError("Normalize is not supported as an output transform.")
+        return v
+
+    @model_validator(mode="after")
+    def _specs(self):
+        """As SingleTaskGPSurrogate: one-hot categoricals, exactly one output."""
+        return _one_hot_single_output(self)
+
+
+class PolynomialSurrogate(BaseModel):
+    """bofire/data_models/surrogates/polynomial.py:12-24 (without the hyperconfig and aggregations):
+    an exact GP with a PolynomialKernel.  Not part of AnySurrogate: it does not enter strategies."""
+    type: Literal["PolynomialSurrogate"] = "PolynomialSurrogate"
+    inputs: Inputs
+    outputs: Outputs
+    input_preprocessing_specs: Dict[str, CategoricalEncodingEnum] = Field(default_factory=dict, validate_default=True)
+    dump: Optional[str] = None
+    scaler: ScalerEnum = ScalerEnum.NORMALIZE
+    output_scaler: ScalerEnum = ScalerEnum.STANDARDIZE
+    kernel: PolynomialKernel = Field(default_factory=lambda: PolynomialKernel(power=2))
+    noise_prior: AnyPrior = Field(default_factory=lambda: THREESIX_NOISE_PRIOR())
+
+    @field_validator("output_scaler")
+    @classmethod
+    def _os(cls, v):
+        if v == ScalerEnum.NORMALIZE:
+            raise ValueError("Normalize is not supported as an output transform.")
+        return v
+
+    @model_validator(mode="after")
+    def _specs(self):
+        """As SingleTaskGPSurrogate: one-hot categoricals, exactly one output."""
+        return _one_hot_single_output(self)
+
+    @staticmethod
+    def from_power(power: int, inputs: Inputs, outputs: Outputs):
+        return PolynomialSurrogate(kernel=PolynomialKernel(power=power), inputs=inputs, outputs=outputs)
+
+
+def _one_hot_single_output(model):
+    """SingleTaskGPSurrogate's model validator for the surrogates that share it
+    (bofire/data_models/surrogates/botorch.py:19-60)."""
+    specs = dict(model.input_preprocessing_specs)
+    for key in model.inputs.get_keys(CategoricalInput):
+        if specs.get(key, CategoricalEncodingEnum.ONE_HOT) != CategoricalEncodingEnum.ONE_HOT:
+            raise ValueError("Botorch based models have to use one hot encodings for categoricals")
+        specs[key] = CategoricalEncodingEnum.ONE_HOT
+    model.__dict__["input_preprocessing_specs"] = specs
+    if len(model.outputs) != 1:
+        raise ValueError(f"{type(model).__name__} takes exactly one output")
+    return model
 
 
 AnySurrogate = Annotated[Union[SingleTaskGPSurrogate], Field(discriminator="type")]

@@ -273,6 +273,19 @@ class MLLEvaluator:
         return ll / n, g
 
 
+def noise_start(noise_prior) -> float:
+    """The fit's start value of the noise: the prior's mode (LogNormal: exp(loc - scale^2); Gamma
+    with concentration > 1: (concentration - 1) / rate), else twice the lower bound."""
+    nzp = _prior(noise_prior)
+    if nzp is not None and nzp[0] == "lognormal":
+        noise0 = math.exp(nzp[1] - nzp[2] ** 2)
+    elif nzp is not None and nzp[0] == "gamma" and nzp[1] > 1:
+        noise0 = (nzp[1] - 1) / nzp[2]
+    else:
+        noise0 = 2 * MIN_INFERRED_NOISE_LEVEL
+    return max(noise0, MIN_INFERRED_NOISE_LEVEL)
+
+
 def fit_single(Xn: torch.Tensor, y_raw: np.ndarray, kind: int, ls_prior, noise_prior=(-4.0, 1.0),
                max_attempts: int = 10, seed: int = 0, options: Optional[dict] = None,
                standardize: bool = True) -> GPHyper:
@@ -291,14 +304,7 @@ def fit_single(Xn: torch.Tensor, y_raw: np.ndarray, kind: int, ls_prior, noise_p
     d = Xn.shape[1]
     lsp, nzp = _prior(ls_prior), _prior(noise_prior)
     ev = MLLEvaluator(Xn, y, kind, lsp, nzp)
-    if nzp is not None and nzp[0] == "lognormal":
-        noise0 = math.exp(nzp[1] - nzp[2] ** 2)
-    elif nzp is not None and nzp[0] == "gamma" and nzp[1] > 1:
-        noise0 = (nzp[1] - 1) / nzp[2]
-    else:
-        noise0 = 2 * MIN_INFERRED_NOISE_LEVEL
-    noise0 = max(noise0, MIN_INFERRED_NOISE_LEVEL)
-    x0 = np.concatenate([[noise0, 0.0], np.zeros(d)])
+    x0 = np.concatenate([[noise_start(nzp), 0.0], np.zeros(d)])
     bounds = [(MIN_INFERRED_NOISE_LEVEL, None), (None, None)] + [(None, None)] * d
     rng = np.random.default_rng(seed)
     last_err = None
@@ -970,3 +976,193 @@ class MixedGPBatch:
         R = ops.gemm(self.M, self.cross(Xc, C))
         return ops.posterior_finalize(R, self.const, self.ym, self.ys, self.kxx,
                                       self.noise if observation_noise else None)
+
+
+# ---------------------------------------------------------------------------------------
+# dot-product GPs ([upstream] SingleTaskGP with a gpytorch LinearKernel / PolynomialKernel, as the
+# reference builds it for LinearSurrogate / PolynomialSurrogate: bofire/surrogates/mapper.py,
+# bofire/kernels/mapper.py)
+# ---------------------------------------------------------------------------------------
+# [upstream] restated (BoTorch and gpytorch are not installed; this is the specification the code
+# follows, parity-unpinned):
+#   inputs    the transformed row, continuous columns with the Normalize bounds of get_scaler,
+#             one-hot blocks identity (SingleTaskGPSurrogate._bounds / transform_inputs)
+#   kernel    power 0:  k(x, x') = v <x, x'>,       v = softplus(raw_v), raw_v = 0 at the start
+#             power p:  k(x, x') = (<x, x'> + c)^p, c = softplus(raw_c), raw_c = 0 at the start
+#             (1 <= p <= 8 on the device); the prior variance k(x, x) depends on x
+#   priors    variance_prior on v / offset_prior on c (optional), the noise prior on the noise
+#   mean      ConstantMean, a direct parameter starting at 0; Gaussian noise a direct parameter
+#             >= 1e-4; raw vector x = [noise, constant, raw_theta]
+#   loss      (MLL + sum log prior) / n on standardised targets, as MLLEvaluator
+#   fit       scipy L-BFGS-B from fit_single's noise start; on NotPSDError noise and theta are
+#             resampled from their priors (a parameter without one keeps its start value),
+#             max_attempts = 10 (bofire/surrogates/single_task_gp.py:71)
+DOT_MAX_POWER = ops.DOT_MAX_POWER
+
+
+def check_dot_power(power) -> int:
+    """0 (linear) or the polynomial degree 1..8 the device kernels are built for."""
+    if isinstance(power, bool) or int(power) != power:
+        raise ValueError(f"power must be an integer, got {power!r}")
+    power = int(power)
+    if not 0 <= power <= DOT_MAX_POWER:
+        raise NotImplementedError(f"dot-product kernels are built for the linear kernel (power 0) and polynomial "
+                                  f"powers 1 <= p <= {DOT_MAX_POWER}, got {power}")
+    return power
+
+
+@dataclass
+class DotGPHyper:
+    power: int                # 0: linear kernel, p >= 1: polynomial kernel of that degree
+    theta: float              # the variance v (linear) or the offset c (polynomial)
+    noise: float
+    constant: float
+    y_mean: float
+    y_std: float
+
+
+class DotMLLEvaluator:
+    """Exact MLL / n with hyperpriors of one dot-product GP on the device; raw parameter vector
+    x = [noise, constant, raw_theta] (theta = softplus(raw_theta)).  The Gram matrix G = Xn Xn^T
+    does not depend on the parameters and is formed once here; an evaluation is the element-wise
+    map of G, the batched Cholesky (psd_safe ladder), alpha, W = alpha alpha^T - K^-1, the fused
+    theta gradient and the scalar terms, and one device-to-host copy."""
+
+    def __init__(self, Xn: torch.Tensor, y_std_space: np.ndarray, power: int, theta_prior, noise_prior):
+        self.Xn = Xn.contiguous()
+        self.n, self.d = Xn.shape
+        self.power = check_dot_power(power)
+        self.y = np.asarray(y_std_space, dtype=np.float64)
+        self.theta_prior = _prior(theta_prior)
+        self.noise_prior = _prior(noise_prior)
+        self.dev = Xn.device
+        self.G = ops.gemm(self.Xn, self.Xn, transB=True)
+
+    def __call__(self, x: np.ndarray):
+        n, dev = self.n, self.dev
+        noise, const, raw = float(x[0]), float(x[1]), float(x[2])
+        theta = float(softplus_np(raw))
+        th_t = torch.tensor([theta], dtype=torch.float64, device=dev)
+        Ky = ops.dot_kernel_apply(self.G, th_t, self.power,
+                                  diag_add=torch.tensor([noise], dtype=torch.float64, device=dev))
+        L, Linv, _, info = ops.cholesky_inverse(Ky, 1e-8, 3, raise_on_fail=False)
+        r = torch.as_tensor((self.y - const)[None, :, None], device=dev)
+        v = ops.gemm(Linv, r)
+        alpha = ops.gemm(Linv, v, transA=True)                       # 1 x n x 1
+        W = ops.gemm(alpha, alpha, transB=True)                      # alpha alpha^T
+        ops.gemm(Linv, Linv, transA=True, alpha=-1.0, beta=1.0, out=W)   # - K^-1
+        gth = ops.dot_kernel_theta_grad(self.G, th_t, W, self.power)
+        terms = ops.mll_terms(L, Linv, r[..., 0].contiguous(), alpha[..., 0].contiguous())
+        out = torch.cat([terms[0], gth, info.to(torch.float64)]).cpu().numpy()   # the evaluation's one copy
+        if out[6] != 0:
+            raise ops.NotPSDError("Matrix not positive definite after repeatedly adding jitter up to 1.0e-06")
+        logdet, quad, trKinv, sum_a, sum_a2 = out[:5]
+        ll = -0.5 * quad - 0.5 * logdet - 0.5 * n * math.log(2 * math.pi)
+        d_noise = 0.5 * (sum_a2 - trKinv)
+        d_const = sum_a
+        d_theta = 0.5 * out[5]
+        if self.theta_prior is not None:
+            ll += float(prior_logpdf_np(self.theta_prior, theta))
+            d_theta += float(prior_dlogpdf_np(self.theta_prior, theta))
+        if self.noise_prior is not None:
+            ll += float(prior_logpdf_np(self.noise_prior, noise))
+            d_noise += float(prior_dlogpdf_np(self.noise_prior, noise))
+        with np.errstate(over="ignore"):     # exp(-raw) = inf at a very negative raw: sigmoid 0, as it should be
+            g = np.array([d_noise, d_const, d_theta * float(sigmoid_np(raw))]) / n
+        return ll / n, g
+
+
+def fit_dot(Xn: torch.Tensor, y_raw: np.ndarray, power: int, theta_prior=None, noise_prior=None,
+            max_attempts: int = 10, seed: int = 0, options: Optional[dict] = None,
+            standardize: bool = True) -> DotGPHyper:
+    """fit_gpytorch_mll of a dot-product GP restated on the device kernels: scipy L-BFGS-B on
+    -MLL / n over x = [noise >= 1e-4, constant, raw_theta] from the noise start of fit_single,
+    constant 0 and raw_theta 0 (theta = ln 2); on NotPSDError noise and theta are resampled from
+    their priors (a parameter without a prior keeps its start value) and the fit is retried
+    (max_attempts = 10, bofire/surrogates/single_task_gp.py:71)."""
+    from scipy.optimize import minimize
+
+    power = check_dot_power(power)
+    y_raw = np.asarray(y_raw, dtype=np.float64)
+    y_mean, y_std = standardize_params(y_raw) if standardize else (0.0, 1.0)
+    thp, nzp = _prior(theta_prior), _prior(noise_prior)
+    ev = DotMLLEvaluator(Xn, (y_raw - y_mean) / y_std, power, thp, nzp)
+    start = np.array([noise_start(nzp), 0.0, 0.0])
+    x0 = start.copy()
+    bounds = [(MIN_INFERRED_NOISE_LEVEL, None), (None, None), (None, None)]
+    rng = np.random.default_rng(seed)
+    last_err = None
+    for _ in range(max_attempts):
+        try:
+            res = minimize(lambda x: tuple(-v for v in ev(x)), x0, jac=True, method="L-BFGS-B", bounds=bounds,
+                           options=options or {})
+            xv = res.x
+            return DotGPHyper(power=power, theta=float(softplus_np(xv[2])), noise=float(xv[0]),
+                              constant=float(xv[1]), y_mean=y_mean, y_std=y_std)
+        except ops.NotPSDError as e:  # sample_all_priors, then retry
+            last_err = e
+            x0 = start.copy()
+            if thp is not None:
+                x0[2] = float(np.log(np.expm1(prior_sample_np(thp, rng, 1)[0])))
+            if nzp is not None:
+                x0[0] = max(float(prior_sample_np(nzp, rng, 1)[0]), MIN_INFERRED_NOISE_LEVEL)
+    raise RuntimeError(f"dot-product GP fit failed after {max_attempts} attempts: {last_err}")
+
+
+class DotGPBatch:
+    """B dot-product GPs of one power on shared normalised training rows Xn (n x d, device); lo /
+    hi (d) are the Normalize bounds of the transformed row (one-hot columns 0 / 1).  Test inputs
+    are raw transformed rows, normalised on the device."""
+
+    mask = None       # every member is trained on every row
+
+    def __init__(self, Xn: torch.Tensor, Y: torch.Tensor, hypers: Sequence[DotGPHyper], lo: torch.Tensor,
+                 hi: torch.Tensor):
+        self.Xn = Xn.contiguous()
+        self.hypers = list(hypers)
+        if not self.hypers:
+            raise ValueError("DotGPBatch needs at least one member")
+        powers = {check_dot_power(h.power) for h in self.hypers}
+        if len(powers) != 1:
+            raise ValueError(f"the members of a DotGPBatch share one power, got {sorted(powers)}")
+        self.power = powers.pop()
+        dev = Xn.device
+        self.device = dev
+        self.B = len(self.hypers)
+        self.n, self.d = Xn.shape
+        self.lo, self.hi = lo, hi
+        self.inv_range = 1.0 / (hi - lo)
+        t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64), device=dev)  # noqa: E731
+        self.theta = t([h.theta for h in self.hypers])
+        self.noise = t([h.noise for h in self.hypers])
+        self.const = t([h.constant for h in self.hypers])
+        self.ym = t([h.y_mean for h in self.hypers])
+        self.ys = t([h.y_std for h in self.hypers])
+        Yc = Y.to(device=dev, dtype=torch.float64).reshape(self.n, self.B).T.contiguous()
+        self.y = ((Yc - self.ym[:, None]) / self.ys[:, None]).contiguous()
+        self.G = ops.gemm(self.Xn, self.Xn, transB=True)
+        self.refresh()
+
+    # -- caches: L = chol(K + s2 I), Linv, alpha, M = [Linv; alpha^T] ----------------------
+    def refresh(self):
+        Ky = ops.dot_kernel_apply(self.G, self.theta, self.power, diag_add=self.noise)
+        self.L, self.Linv, _, _ = ops.cholesky_inverse(Ky, 1e-8, 3)
+        r = (self.y - self.const[:, None]).unsqueeze(-1).contiguous()           # B x n x 1
+        v = ops.gemm(self.Linv, r)
+        self.alpha = ops.gemm(self.Linv, v, transA=True)[..., 0].contiguous()  # B x n
+        self.M = torch.cat([self.Linv, self.alpha.unsqueeze(1)], dim=1).contiguous()  # B x (n+1) x n
+
+    def kernel_train(self, noise: bool = False) -> torch.Tensor:
+        return ops.dot_kernel_apply(self.G, self.theta, self.power, diag_add=self.noise if noise else None)
+
+    def cross(self, Xraw: torch.Tensor) -> torch.Tensor:
+        """K(Xtr, normalize(Xraw)) : B x n x nt."""
+        Xraw = Xraw.to(device=self.device, dtype=torch.float64)
+        Xt = ((Xraw - self.lo) * self.inv_range).contiguous()
+        return ops.dot_kernel_apply(ops.gemm(self.Xn, Xt, transB=True), self.theta, self.power)
+
+    def posterior(self, Xraw: torch.Tensor, observation_noise: bool = False):
+        """Mean and variance (B x nt) at raw (transformed, unnormalised) inputs (evr_dot_gp_posterior)."""
+        Xraw = Xraw.to(device=self.device, dtype=torch.float64).contiguous()
+        return ops.dot_gp_posterior(self.Xn, Xraw, self.lo, self.inv_range, self.theta, self.M, self.power,
+                                    self.const, self.ym, self.ys, self.noise if observation_noise else None)

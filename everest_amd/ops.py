@@ -260,6 +260,91 @@ def mixed_kernel_cross_grad(Xc, C, X2c, C2, params, G, scale, cont_idx, kind: in
     return dX
 
 
+# powers of the dot-product kernel entry points (include/everest_amd.h): 0 = linear, p = polynomial
+DOT_MAX_POWER = 8
+
+
+def _dot_args(G, theta, power, name: str):
+    if isinstance(power, bool) or int(power) != power:
+        raise ValueError(f"{name}: power must be an integer, got {power!r}")
+    G, theta = _dev(G, f"{name}: G"), _dev(theta, f"{name}: theta")
+    if G.dim() != 2 or theta.dim() != 1 or theta.numel() < 1:
+        raise ValueError(f"{name}: G {tuple(G.shape)} must be n1 x n2 and theta {tuple(theta.shape)} a vector of B >= 1 "
+                         "values")
+    return G, theta, int(power)
+
+
+def _dot_call(symbol: str, power: int, *args):
+    """The native call; a power the kernels are not built for (the library's own error, never a
+    silent fall-through) surfaces as NotImplementedError."""
+    try:
+        call(symbol, *args)
+    except RuntimeError as e:
+        if not 0 <= power <= DOT_MAX_POWER:
+            raise NotImplementedError(str(e)) from e
+        raise
+
+
+def dot_kernel_apply(G, theta, power: int, diag_add=None) -> torch.Tensor:
+    """K[b] (B x n1 x n2) of the dot-product kernels on the Gram matrix G = X1n X2n^T (n1 x n2, shared by
+    the members; evr_dot_kernel_apply): power 0 the linear kernel theta_b g, power p in 1..8 the polynomial
+    kernel (g + theta_b)^p (+ diag_add_b on i == j).  theta: B values."""
+    G, theta, power = _dot_args(G, theta, power, "dot_kernel_apply")
+    B, (n1, n2) = theta.numel(), G.shape
+    dg = None if diag_add is None else _dev(diag_add, "diag_add")
+    if dg is not None and dg.numel() != B:
+        raise ValueError(f"dot_kernel_apply: diag_add holds {dg.numel()} values for {B} members")
+    K = torch.empty(B, n1, n2, dtype=torch.float64, device=G.device)
+    _dot_call("evr_dot_kernel_apply", power, _stream(), power, B, n1, n2, G.data_ptr(), theta.data_ptr(), _p(dg),
+              K.data_ptr())
+    return K
+
+
+def dot_kernel_theta_grad(G, theta, W, power: int) -> torch.Tensor:
+    """g[b] = sum_ij W[b][i][j] dk/dtheta(G[i][j]; theta_b) (B values) in one pass over W (B x n x n, need
+    not be symmetric) and G (n x n); evr_dot_kernel_theta_grad.  Bitwise reproducible."""
+    G, theta, power = _dot_args(G, theta, power, "dot_kernel_theta_grad")
+    W = _dev(W, "W")
+    B, n = theta.numel(), G.shape[0]
+    if G.shape[1] != n or tuple(W.shape) != (B, n, n):
+        raise ValueError(f"dot_kernel_theta_grad: G {tuple(G.shape)} must be n x n and W {tuple(W.shape)} "
+                         f"{(B, n, n)}")
+    g = torch.empty(B, dtype=torch.float64, device=G.device)
+    if n == 0:
+        return g.zero_()
+    work = torch.empty(B, n, dtype=torch.float64, device=G.device)
+    _dot_call("evr_dot_kernel_theta_grad", power, _stream(), power, B, n, G.data_ptr(), theta.data_ptr(),
+              W.data_ptr(), g.data_ptr(), work.data_ptr())
+    return g
+
+
+def dot_gp_posterior(Xn, X, shift, scale, theta, M, power: int, c, ym, ys, noise_add=None):
+    """Mean and variance (B x nt) of B dot-product GPs in one native call (evr_dot_gp_posterior): the raw
+    rows X (nt x d) are normalised as (X - shift) * scale, K* = f(Xn Xt^T), R = M K* with
+    M = [Linv; alpha^T] (B x (n+1) x n), and the prior variance of each test point comes from its own row."""
+    if isinstance(power, bool) or int(power) != power:
+        raise ValueError(f"dot_gp_posterior: power must be an integer, got {power!r}")
+    power = int(power)
+    Xn, X, M, theta = _dev(Xn, "Xn"), _dev(X, "X"), _dev(M, "M"), _dev(theta, "theta")
+    if M.dim() != 3 or Xn.dim() != 2 or X.dim() != 2 or theta.dim() != 1:
+        raise ValueError("dot_gp_posterior: M must be B x (n+1) x n, Xn n x d, X nt x d and theta a vector")
+    B, n1, n = M.shape
+    nt, d = X.shape
+    aux = [_dev(t, "aux") for t in (shift, scale, c, ym, ys)]
+    na = None if noise_add is None else _dev(noise_add, "noise")
+    if (n1 != n + 1 or tuple(Xn.shape) != (n, d) or theta.numel() != B or aux[0].numel() != d or aux[1].numel() != d
+            or any(a.numel() != B for a in aux[2:]) or (na is not None and na.numel() != B)):
+        raise ValueError(f"dot_gp_posterior: shape mismatch (M {tuple(M.shape)}, Xn {tuple(Xn.shape)}, X "
+                         f"{tuple(X.shape)}, theta {tuple(theta.shape)})")
+    mean = torch.empty(B, nt, dtype=torch.float64, device=X.device)
+    var = torch.empty_like(mean)
+    work = _workspace(_native.load().evr_dot_gp_posterior_workspace_doubles(B, n, nt, d), X.device)
+    _dot_call("evr_dot_gp_posterior", power, _stream(), power, B, n, nt, d, Xn.data_ptr(), X.data_ptr(),
+              aux[0].data_ptr(), aux[1].data_ptr(), theta.data_ptr(), M.data_ptr(), aux[2].data_ptr(),
+              aux[3].data_ptr(), aux[4].data_ptr(), _p(na), mean.data_ptr(), var.data_ptr(), work.data_ptr())
+    return mean, var
+
+
 def mll_terms(L, Linv, r, alpha) -> torch.Tensor:
     """B x 5: logdet, quad, tr(K^-1), sum(alpha), sum(alpha^2)."""
     L, Linv, r, alpha = _dev(L, "L"), _dev(Linv, "Linv"), _dev(r, "r"), _dev(alpha, "alpha")

@@ -1,6 +1,8 @@
 """Functional surrogates on the device — mirrors bofire/surrogates/{single_task_gp,botorch,
 surrogate,trainable,botorch_surrogates}.py for ``SingleTaskGPSurrogate``, and
-bofire/surrogates/mixed_single_task_gp.py for ``MixedSingleTaskGPSurrogate``.
+bofire/surrogates/mixed_single_task_gp.py for ``MixedSingleTaskGPSurrogate``; ``LinearSurrogate``
+and ``PolynomialSurrogate`` (SingleTaskGP with a dot-product kernel in the reference) share
+``DotProductGPSurrogate``.
 
 The fitted model (transformed training inputs, targets, hyperparameters, Normalize bounds,
 kernel family) is the wire format of ``dumps()/loads()`` — a versioned JSON + base64(npz)
@@ -548,6 +550,152 @@ class MixedSingleTaskGPSurrogate:
         self._set_state(arr["X"], arr["y"], arr["lo"], arr["hi"], meta["kind"], hyp)
 
 
+class DotProductGPSurrogate:
+    """Exact GP with a dot-product kernel for one output: the device side of ``LinearSurrogate``
+    (k = v <x, x'>) and ``PolynomialSurrogate`` (k = (<x, x'> + c)^p, 1 <= p <= 8), which the
+    reference maps onto SingleTaskGPSurrogate with a gpytorch LinearKernel / PolynomialKernel
+    (bofire/surrogates/mapper.py; the model is restated in gp.py).  Inputs are transformed and
+    normalised as SingleTaskGPSurrogate does."""
+
+    FORMAT = "everest_amd.DotProductGP/1"
+
+    def __init__(self, data_model):
+        from .gp import check_dot_power
+
+        self.data_model = data_model
+        self.inputs = data_model.inputs
+        self.outputs = data_model.outputs
+        self.kernel = data_model.kernel
+        if self.kernel.features is not None:
+            raise NotImplementedError("kernel.features (a kernel on a subset of the inputs) is out of scope for the "
+                                      "MI355X build")
+        if isinstance(self.kernel, dm.LinearKernel):
+            self.power, self.theta_prior = 0, self.kernel.variance_prior
+        else:
+            if self.kernel.power < 1:
+                raise NotImplementedError(f"PolynomialKernel power must be an integer 1 <= p <= 8 on the device, "
+                                          f"got {self.kernel.power}")
+            self.power, self.theta_prior = check_dot_power(self.kernel.power), self.kernel.offset_prior
+        self.noise_prior = data_model.noise_prior
+        self.scaler = data_model.scaler
+        self.output_scaler = data_model.output_scaler
+        self.input_preprocessing_specs = {k: v.value if hasattr(v, "value") else v
+                                          for k, v in data_model.input_preprocessing_specs.items()}
+        self.state: Optional[dict] = None
+        self.gp = None
+        if data_model.dump is not None:
+            self.loads(data_model.dump)
+
+    @property
+    def is_fitted(self) -> bool:
+        return self.state is not None
+
+    @property
+    def output_key(self) -> str:
+        return self.outputs.get_keys()[0]
+
+    # ---- transforms ----------------------------------------------------------------
+    _bounds = SingleTaskGPSurrogate._bounds
+    transform_inputs = SingleTaskGPSurrogate.transform_inputs
+    _preprocess_experiments = SingleTaskGPSurrogate._preprocess_experiments
+    _fit_data = SingleTaskGPSurrogate._fit_data
+
+    # ---- fit -------------------------------------------------------------------------
+    def fit(self, experiments: pd.DataFrame, options: Optional[dict] = None):
+        """TrainableSurrogate.fit (bofire/surrogates/trainable.py:24-42): valid rows of this output."""
+        X, Y = self._fit_data(experiments)
+        self._fit(X, Y, options)
+
+    def _fit(self, X: pd.DataFrame, Y: pd.DataFrame, options: Optional[dict] = None):
+        from .gp import fit_dot
+
+        Xt = self.transform_inputs(X)
+        lo, hi = self._bounds(X)
+        y = Y.values[:, 0].astype(np.float64)
+        Xn = torch.as_tensor((Xt - lo) / (hi - lo), dtype=torch.float64, device=device())
+        hyp = fit_dot(Xn, y, self.power, map_prior(self.theta_prior, 1), map_prior(self.noise_prior, 1),
+                      options=options, standardize=self.output_scaler == ScalerEnum.STANDARDIZE)
+        self._set_state(Xt, y, lo, hi, hyp)
+
+    def _set_state(self, Xt, y, lo, hi, hyp):
+        self.state = dict(X=np.asarray(Xt), y=np.asarray(y), lo=np.asarray(lo), hi=np.asarray(hi),
+                          power=int(hyp.power), theta=float(hyp.theta), noise=float(hyp.noise),
+                          constant=float(hyp.constant), y_mean=float(hyp.y_mean), y_std=float(hyp.y_std))
+        self.gp = self._build_gp()
+
+    def hyper(self):
+        from .gp import DotGPHyper
+
+        s = self.state
+        return DotGPHyper(power=s["power"], theta=s["theta"], noise=s["noise"], constant=s["constant"],
+                          y_mean=s["y_mean"], y_std=s["y_std"])
+
+    def _build_gp(self):
+        from .gp import DotGPBatch
+
+        s = self.state
+        dev = device()
+        t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64), device=dev)  # noqa: E731
+        Xn = t((s["X"] - s["lo"]) / (s["hi"] - s["lo"]))
+        return DotGPBatch(Xn, t(s["y"][:, None]), [self.hyper()], t(s["lo"]), t(s["hi"]))
+
+    # ---- predict ----------------------------------------------------------------------
+    def predict(self, experiments: pd.DataFrame) -> pd.DataFrame:
+        """Surrogate.predict (bofire/surrogates/surrogate.py:39-67): posterior(observation_noise=True)."""
+        if not self.is_fitted:
+            raise ValueError("Model is not fitted/available yet.")
+        Xt = self.transform_inputs(experiments[self.inputs.get_keys()])
+        mean, var = self.gp.posterior(torch.as_tensor(Xt, dtype=torch.float64, device=self.gp.device),
+                                      observation_noise=True)
+        key = self.output_key
+        return pd.DataFrame({f"{key}_pred": mean[0].cpu().numpy(), f"{key}_sd": np.sqrt(var[0].cpu().numpy())},
+                            index=experiments.index)
+
+    # ---- cross-validation --------------------------------------------------------------
+    def cross_validate(self, experiments: pd.DataFrame, folds: int = -1, include_X: bool = False,
+                       include_labcodes: bool = False, random_state: Optional[int] = None,
+                       stratified_feature: Optional[str] = None, group_split_column: Optional[str] = None,
+                       hooks: Optional[Dict[str, Callable]] = None,
+                       hook_kwargs: Optional[Dict[str, Dict[str, Any]]] = None
+                       ) -> Tuple[CvResults, CvResults, Dict[str, list]]:
+        """TrainableSurrogate.cross_validate (bofire/surrogates/trainable.py:79-339), arguments and
+        return value as SingleTaskGPSurrogate.cross_validate: the plain sequential loop, a fresh
+        surrogate per fold.  This surrogate's own fitted state is left as it was."""
+        return run_cross_validation(self, lambda ex, splits: cv_sequential(self, ex, splits), experiments, folds,
+                                    include_X, include_labcodes, random_state, stratified_feature,
+                                    group_split_column, hooks, hook_kwargs)
+
+    # ---- dump / load ------------------------------------------------------------------
+    def dumps(self) -> str:
+        if not self.is_fitted:
+            raise ValueError("Model is not fitted/available yet.")
+        buf = io.BytesIO()
+        s = self.state
+        np.savez(buf, X=s["X"], y=s["y"], lo=s["lo"], hi=s["hi"])
+        meta = {"format": self.FORMAT, "power": s["power"], "theta": s["theta"], "noise": s["noise"],
+                "constant": s["constant"], "y_mean": s["y_mean"], "y_std": s["y_std"],
+                "arrays": base64.b64encode(buf.getvalue()).decode()}
+        return base64.b64encode(json.dumps(meta).encode()).decode()
+
+    def loads(self, data: str):
+        from .gp import DotGPHyper
+
+        try:
+            meta = json.loads(base64.b64decode(data.encode()).decode())
+        except Exception as e:
+            raise ValueError(f"not a {self.FORMAT} dump") from e
+        if not isinstance(meta, dict) or meta.get("format") != self.FORMAT:
+            raise ValueError(f"not a {self.FORMAT} dump (format "
+                             f"{meta.get('format') if isinstance(meta, dict) else None!r})")
+        if int(meta["power"]) != self.power:
+            raise ValueError(f"dump of a power-{meta['power']} model does not fit this surrogate's kernel "
+                             f"(power {self.power})")
+        arr = np.load(io.BytesIO(base64.b64decode(meta["arrays"])), allow_pickle=False)
+        hyp = DotGPHyper(power=int(meta["power"]), theta=meta["theta"], noise=meta["noise"],
+                         constant=meta["constant"], y_mean=meta["y_mean"], y_std=meta["y_std"])
+        self._set_state(arr["X"], arr["y"], arr["lo"], arr["hi"], hyp)
+
+
 class BotorchSurrogates:
     """bofire/surrogates/botorch_surrogates.py:19-128."""
 
@@ -728,9 +876,12 @@ def union_rows(Xs):
 
 
 def map(data_model):
-    """bofire/surrogates/mapper.py:21-44 (SingleTaskGPSurrogate and MixedSingleTaskGPSurrogate)."""
+    """bofire/surrogates/mapper.py:21-44 (SingleTaskGPSurrogate, MixedSingleTaskGPSurrogate, and
+    LinearSurrogate / PolynomialSurrogate, which share DotProductGPSurrogate)."""
     if isinstance(data_model, dm.SingleTaskGPSurrogate):
         return SingleTaskGPSurrogate(data_model)
+    if isinstance(data_model, (dm.LinearSurrogate, dm.PolynomialSurrogate)):
+        return DotProductGPSurrogate(data_model)
     if isinstance(data_model, dm.MixedSingleTaskGPSurrogate):
         return MixedSingleTaskGPSurrogate(data_model)
     if isinstance(data_model, dm.BotorchSurrogates):

@@ -118,6 +118,42 @@ int evr_mixed_kernel_cross_grad(void* stream, int kind, int B, int n, int rows, 
                                 const double* params, const double* scale, const int* cont_idx, const double* G,
                                 double* dX, double* work);
 
+/* ---- dot-product kernels ([upstream] gpytorch LinearKernel / PolynomialKernel behind
+ * bofire/data_models/surrogates/linear.py and polynomial.py) --------------------------------
+ * Functions of the Gram matrix G = X1n X2n^T of the normalised inputs (evr_gemm_f64, transB):
+ *   power = 0        k = theta g                 theta = the variance v
+ *   power = p in 1..8  k = (g + theta)^p         theta = the offset c
+ * theta: B doubles, one per member.  Powers are formed by repeated multiplication in one fixed
+ * order, never through pow(): t = g + theta, r_1 = t, r_{k+1} = r_k t, k = r_p; the theta
+ * derivative is g (power 0), exactly 1 (p = 1) and (double)p r_{p-1} (p >= 2).  The kernels are
+ * not stationary: the prior variance k(x, x) = theta |x|^2 or (|x|^2 + theta)^p depends on x.
+ * A power outside 0..8 is an error.
+ *
+ * K[b][i][j] = f(G[i][j]; theta_b) (+ diag_add[b] where i == j; diag_add may be NULL).  G: n1 x n2,
+ * shared by the members; K: B x n1 x n2.  G and K must not alias.  Element-wise, so a symmetric G
+ * gives a bitwise symmetric K.  n1 n2 = 0 returns 0 without a launch; n1 n2 < 2^31. */
+int evr_dot_kernel_apply(void* stream, int power, int B, int n1, int n2, const double* G, const double* theta,
+                         const double* diag_add, double* K);
+/* g[b] = sum_{i,j} W[b][i][j] df/dtheta(G[i][j]; theta_b) in one pass over W (B x n x n, need not be
+ * symmetric) and G (n x n).  work: B*n doubles (per-row partials, summed in a fixed order: no
+ * atomics, bitwise reproducible). */
+int evr_dot_kernel_theta_grad(void* stream, int power, int B, int n, const double* G, const double* theta,
+                              const double* W, double* g, double* work);
+/* Whole posterior in one call, on the model of evr_gp_posterior: the test rows are normalised
+ * ((X - shift) * scale per column, exactly that subtraction and product; NULL = identity), the
+ * cross Gram Xn Xt^T, evr_dot_kernel_apply, R = M K* with M = [Linv; alpha^T] (B x (n+1) x n), and
+ *   mean[b][t] = ym[b] + ys[b] (c[b] + R[b][n][t])
+ *   var[b][t]  = ys[b]^2 (k_b(x_t, x_t) - sum_{i<n} R[b][i][t]^2 + noise_add[b])
+ * with k_b(x_t, x_t) from the test point's own normalised row (|x_t|^2 summed in column order).
+ * R's columns are reduced in a fixed order.  Xn: n x d normalised training rows, X: nt x d raw.
+ * work: evr_dot_gp_posterior_workspace_doubles(B, n, nt, d) doubles, 16-byte aligned.  nt = 0
+ * returns 0 without a launch. */
+long long evr_dot_gp_posterior_workspace_doubles(int B, int n, int nt, int d);
+int evr_dot_gp_posterior(void* stream, int power, int B, int n, int nt, int d, const double* Xn, const double* X,
+                         const double* shift, const double* scale, const double* theta, const double* M,
+                         const double* c, const double* ym, const double* ys, const double* noise_add, double* mean,
+                         double* var, double* work);
+
 /* Native MLL plan for the GP fit: B exact GPs sharing the normalised inputs Xn (n x d,
  * device, must outlive the plan) with standardised targets Y (B x n, device, copied).  One
  * evr_mll_plan_eval is one hipGraph launch computing, per member b, with params (host) =
