@@ -198,6 +198,13 @@ _SIGS = {
     "evr_kernel_lengthscale_grad_members": ([c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 5, c_int),
     "evr_mll_plan_create_members": ([c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4, c_int),
     "evr_mll_assemble_members": ([c_int, c_void_p, c_int] + [c_void_p] * 6, c_int),
+    "evr_kernel_hyper_grad": ([c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 6, c_int),
+    "evr_kernel_hyper_grad_members": ([c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 7, c_int),
+    "evr_kernel_matrix_members_scaled": ([c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 6, c_int),
+    "evr_mll_plan_create_scaled": ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "evr_mll_plan_create_scaled_members": ([c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4, c_int),
+    "evr_mll_assemble_scaled": ([c_int, c_int, c_int] + [c_void_p] * 7, c_int),
+    "evr_mll_assemble_scaled_members": ([c_int, c_void_p, c_int] + [c_void_p] * 7, c_int),
     "evr_lbfgsb_advance": ([c_void_p, c_double] + [c_void_p] * 6 + [c_int, c_int], c_int),
     "evr_qnehvi_plan_eval_host": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "evr_qnehvi_plan_destroy": ([c_void_p], None),

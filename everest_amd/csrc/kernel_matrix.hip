@@ -622,11 +622,54 @@ int kcross_grad_launch(hipStream_t s, int kind, int B, int n1, int n2, int d, co
 // W = alpha alpha^T - K^-1 is exactly 0 off the diagonal of every padded row and column (its
 // product with the finite dK/dls of the finite padded inputs adds 0), and a diagonal entry has
 // distance 0, i.e. sq[k] = 0: padded entries add exact zeros to the member's own sum.
+//
+// SCALED (evr_kernel_hyper_grad[_members], k = sigma^2 k_base): two trailing arguments more, the
+// outputscales and (member form) nvalid.  One accumulator more, sum_j W_ij k_base(d2_ij), summed in
+// the same lane order, and the lengthscale partials times sigma^2; k_base and kernel_dscale come
+// from one exponential (kernel_value_dscale); the row partials are d + 1 wide.  The padding is not
+// free for that sum (a padded row's diagonal has W = -1 and k_base = 1), so the member form sums
+// over i, j < nvalid[b] and writes zeros for the padded rows.  The unscaled instantiations have an
+// empty pack: their arguments and their code are what they were.
+// The price of leaving the unscaled bodies untouched (their registers are pinned):
+// the pair loop now stands four times in this file — unscaled and SCALED, in kls_grad_kernel and in
+// kls_grad_block_kernel — and a fix to it has to be made in all four.
 constexpr int KLS_ROWS = 4;
-template <int MAXD, bool MEMBERS = false>
+struct KlsScaled {
+  const double* os;
+  const int* nvalid;
+};
+__device__ __forceinline__ KlsScaled kls_scaled() { return {nullptr, nullptr}; }
+__device__ __forceinline__ KlsScaled kls_scaled(const double* os, const int* nvalid) { return {os, nvalid}; }
+
+// k_base(d2) and kernel_dscale(kind, d2) from one exponential
+__device__ __forceinline__ void kernel_value_dscale(int kind, double d2, double& kv, double& ds) {
+  if (kind == RBF) {
+    kv = exp_k(-0.5 * d2);
+    ds = -kv;
+    return;
+  }
+  const bool tiny = d2 < 1e-30;   // clamp_min(1e-30): the value is k(1e-15), the gradient 0
+  const double dd = sqrt(fmax(d2, 1e-30));
+  if (kind == MATERN05) {
+    kv = exp_k(-dd);
+    ds = tiny ? 0.0 : -kv / dd;
+  } else if (kind == MATERN15) {
+    const double s = 1.7320508075688772 * dd, e = exp_k(-s);
+    kv = (1.0 + s) * e;
+    ds = tiny ? 0.0 : -3.0 * e;
+  } else {
+    const double s = 2.23606797749979 * dd, e = exp_k(-s);
+    kv = (1.0 + s + (5.0 / 3.0) * d2) * e;
+    ds = tiny ? 0.0 : -(5.0 / 3.0) * (1.0 + s) * e;
+  }
+}
+
+template <int MAXD, bool MEMBERS = false, class... SC>
 __global__ __launch_bounds__(256) void kls_grad_kernel(int kind, int n, int d, const double* __restrict__ X,
                                                        const double* __restrict__ ls,
-                                                       const double* __restrict__ W, double* __restrict__ part) {
+                                                       const double* __restrict__ W, double* __restrict__ part,
+                                                       SC... sc) {
+  constexpr bool SCALED = sizeof...(SC) > 0;
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * KLS_ROWS + (threadIdx.x >> 6);
@@ -635,6 +678,64 @@ __global__ __launch_bounds__(256) void kls_grad_kernel(int kind, int n, int d, c
   const double* lsb = ls + (size_t)b * d;
   const double* Wr = W + ((size_t)b * n + i) * n;
   const int kb = kind_of(kind, b);
+  if constexpr (SCALED) {
+    // the scaled form, apart: columns j < nj (the member's own), the value accumulator, sigma^2
+    const KlsScaled q = kls_scaled(sc...);
+    const int nj = MEMBERS ? min(q.nvalid[b], n) : n;
+    double* pr = part + ((size_t)b * n + i) * (d + 1);
+    if (i >= nj) {   // a padded row: exactly nothing (whole wave)
+      if (lane <= d) pr[lane] = 0.0;
+      return;
+    }
+    const double osb = q.os[b];
+    double xi[MAXD], il[MAXD], acc[MAXD], accv = 0.0;
+#pragma unroll
+    for (int k = 0; k < MAXD; ++k) {
+      xi[k] = k < d ? X[(size_t)i * d + k] : 0.0;
+      il[k] = k < d ? 1.0 / lsb[k] : 0.0;
+      acc[k] = 0.0;
+    }
+    constexpr int UJ = MAXD <= 8 ? 4 : 1;
+    for (int j0 = 0; j0 < nj; j0 += 64 * UJ) {
+      double w[UJ];
+#pragma unroll
+      for (int u = 0; u < UJ; ++u) w[u] = Wr[min(j0 + lane + 64 * u, nj - 1)];
+#pragma unroll
+      for (int u = 0; u < UJ; ++u) {
+        const int j = j0 + lane + 64 * u;
+        if (j >= nj) break;
+        double sq[MAXD];
+        double d2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < MAXD; ++k)
+          if (k < d) {
+            const double df = (xi[k] - X[(size_t)j * d + k]) * il[k];
+            sq[k] = df * df;
+            d2 += sq[k];
+          }
+        double kv, ds;
+        kernel_value_dscale(kb, d2, kv, ds);
+        accv = fma(w[u], kv, accv);
+        const double s = -w[u] * ds;
+#pragma unroll
+        for (int k = 0; k < MAXD; ++k)
+          if (k < d) acc[k] = fma(s, sq[k] * il[k], acc[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < MAXD; ++k) {
+      if (k < d) {
+        double v = acc[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) pr[k] = osb * v;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) accv += __shfl_xor(accv, o, 64);
+    if (lane == 0) pr[d] = accv;
+    return;
+  }
   double xi[MAXD], il[MAXD];
 #pragma unroll
   for (int k = 0; k < MAXD; ++k) {
@@ -684,10 +785,14 @@ __global__ __launch_bounds__(256) void kls_grad_kernel(int kind, int n, int d, c
 
 // Above 16 dims: one block per (row i, output b), 256 threads over j (the wave-per-row form's
 // per-lane (dimension x column) arrays do not stay in registers there).
-template <int MAXD, bool MEMBERS = false>
+// SCALED: as kls_grad_kernel's; red[256] is exactly 4 MAXD at MAXD = 64, so the value column's four
+// wave partials have an array of their own.
+template <int MAXD, bool MEMBERS = false, class... SC>
 __global__ __launch_bounds__(256) void kls_grad_block_kernel(int kind, int n, int d, const double* __restrict__ X,
                                                        const double* __restrict__ ls,
-                                                       const double* __restrict__ W, double* __restrict__ part) {
+                                                       const double* __restrict__ W, double* __restrict__ part,
+                                                       SC... sc) {
+  constexpr bool SCALED = sizeof...(SC) > 0;
   const int b = blockIdx.y;
   const int i = blockIdx.x;
   const int tid = threadIdx.x;
@@ -695,6 +800,62 @@ __global__ __launch_bounds__(256) void kls_grad_block_kernel(int kind, int n, in
   const double* lsb = ls + (size_t)b * d;
   const double* Wb = W + (size_t)b * n * n;
   __shared__ double red[256];
+  if constexpr (SCALED) {
+    __shared__ double redv[4];
+    const KlsScaled q = kls_scaled(sc...);
+    const int nj = MEMBERS ? min(q.nvalid[b], n) : n;
+    double* pr = part + ((size_t)b * n + i) * (d + 1);
+    if (i >= nj) {   // a padded row: exactly nothing (whole workgroup, before any barrier)
+      if (tid <= d) pr[tid] = 0.0;
+      return;
+    }
+    const double osb = q.os[b];
+    double xi[MAXD], il[MAXD], acc[MAXD], accv = 0.0;
+#pragma unroll
+    for (int k = 0; k < MAXD; ++k) {
+      if (k < d) {
+        xi[k] = X[(size_t)i * d + k];
+        il[k] = 1.0 / lsb[k];
+      }
+      acc[k] = 0.0;
+    }
+    for (int j = tid; j < nj; j += 256) {
+      const double w = Wb[(size_t)i * n + j];
+      double sq[MAXD];
+      double d2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < MAXD; ++k)
+        if (k < d) {
+          const double df = (xi[k] - X[(size_t)j * d + k]) * il[k];
+          sq[k] = df * df;
+          d2 += sq[k];
+        }
+      double kv, ds;
+      kernel_value_dscale(kind_of(kind, b), d2, kv, ds);
+      accv = fma(w, kv, accv);
+      const double s = -w * ds;
+#pragma unroll
+      for (int k = 0; k < MAXD; ++k)
+        if (k < d) acc[k] = fma(s, sq[k] * il[k], acc[k]);
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < MAXD; ++k) {
+      if (k < d) {
+        double v = acc[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) red[wave * MAXD + k] = v;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) accv += __shfl_xor(accv, o, 64);
+    if (lane == 0) redv[wave] = accv;
+    __syncthreads();
+    if (tid < d) pr[tid] = osb * (((red[tid] + red[MAXD + tid]) + red[2 * MAXD + tid]) + red[3 * MAXD + tid]);
+    if (tid == 0) pr[d] = ((redv[0] + redv[1]) + redv[2]) + redv[3];
+    return;
+  }
   double xi[MAXD], il[MAXD];
 #pragma unroll
   for (int k = 0; k < MAXD; ++k)
@@ -741,6 +902,9 @@ __global__ __launch_bounds__(256) void kls_grad_block_kernel(int kind, int n, in
 }
 
 // out[b][k] = sum_i part[b][i][k]: one block per (b, k), strided partials + fixed LDS tree
+// SPLIT (evr_kernel_hyper_grad: d counts the value column): the last column goes behind the
+// others, out = [B x (d - 1) | B]
+template <bool SPLIT = false>
 __global__ __launch_bounds__(256) void colsum_kernel(int B, int n, int d, const double* __restrict__ part,
                                                      double* __restrict__ out) {
   const int b = blockIdx.x / d, k = blockIdx.x % d;
@@ -753,7 +917,11 @@ __global__ __launch_bounds__(256) void colsum_kernel(int B, int n, int d, const 
     if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) out[(size_t)b * d + k] = red[0];
+  if constexpr (SPLIT) {
+    if (threadIdx.x == 0) out[k < d - 1 ? (size_t)b * (d - 1) + k : (size_t)B * (d - 1) + b] = red[0];
+  } else {
+    if (threadIdx.x == 0) out[(size_t)b * d + k] = red[0];
+  }
 }
 
 // Scalars of the exact MLL per output b:
@@ -1197,9 +1365,53 @@ static int kls_grad_launch(hipStream_t s, bool members, int kind, int B, int n, 
 #undef LAUNCHB
 #undef LAUNCH
   EVR_LAUNCH_CHECK();
-  colsum_kernel<<<B * d, 256, 0, s>>>(B, n, d, work, gls);
+  colsum_kernel<><<<B * d, 256, 0, s>>>(B, n, d, work, gls);
   EVR_LAUNCH_CHECK();
   return 0;
+}
+
+// evr_kernel_hyper_grad and its member form (nvalid): the SCALED instantiations
+static int khyper_grad_launch(hipStream_t s, int kind, int B, int n, int d, const double* X, const int* nvalid,
+                              const double* lengthscales, const double* os, const double* W, double* out,
+                              double* work) {
+  dim3 grid(cdiv(n, KLS_ROWS), B), gridb(n, B);
+#define LAUNCH(KERNEL, GRID, MD)                                                                              \
+  do {                                                                                                        \
+    if (nvalid)                                                                                               \
+      KERNEL<MD, true, const double*, const int*><<<GRID, 256, 0, s>>>(kind, n, d, X, lengthscales, W, work, os, \
+                                                                       nvalid);                               \
+    else                                                                                                      \
+      KERNEL<MD, false, const double*, const int*><<<GRID, 256, 0, s>>>(kind, n, d, X, lengthscales, W, work, os, \
+                                                                        nvalid);                              \
+  } while (0)
+  if (d <= 8) LAUNCH(kls_grad_kernel, grid, 8);
+  else if (d <= 16) LAUNCH(kls_grad_kernel, grid, 16);
+  else if (d <= 32) LAUNCH(kls_grad_block_kernel, gridb, 32);
+  else LAUNCH(kls_grad_block_kernel, gridb, 64);
+#undef LAUNCH
+  EVR_LAUNCH_CHECK();
+  colsum_kernel<true><<<B * (d + 1), 256, 0, s>>>(B, n, d + 1, work, out);
+  EVR_LAUNCH_CHECK();
+  return 0;
+}
+
+int evr_kernel_hyper_grad(void* stream, int kind, int B, int n, int d, const double* X, const double* lengthscales,
+                          const double* outputscale, const double* W, double* out, double* work) {
+  EVR_CHECK(kind_code_ok(kind, B) && B >= 1 && n >= 1 && d >= 1 && d <= KMAXD && X && lengthscales && outputscale &&
+                W && out,
+            "evr_kernel_hyper_grad: bad args");
+  EVR_CHECK(work != nullptr, "evr_kernel_hyper_grad: work (B*n*(d+1) doubles) required");
+  return khyper_grad_launch((hipStream_t)stream, kind, B, n, d, X, nullptr, lengthscales, outputscale, W, out, work);
+}
+
+int evr_kernel_hyper_grad_members(void* stream, int kind, int B, int n, int d, const double* Xb, const int* nvalid,
+                                  const double* lengthscales, const double* outputscale, const double* W, double* out,
+                                  double* work) {
+  EVR_CHECK(kind >= 0 && kind <= 3 && B >= 1 && n >= 1 && d >= 1 && d <= KMAXD && Xb && nvalid && lengthscales &&
+                outputscale && W && out,
+            "evr_kernel_hyper_grad_members: bad args");
+  EVR_CHECK(work != nullptr, "evr_kernel_hyper_grad_members: work (B*n*(d+1) doubles) required");
+  return khyper_grad_launch((hipStream_t)stream, kind, B, n, d, Xb, nvalid, lengthscales, outputscale, W, out, work);
 }
 
 int evr_kernel_lengthscale_grad(void* stream, int kind, int B, int n, int d, const double* X,
@@ -1218,8 +1430,10 @@ int evr_kernel_lengthscale_grad_members(void* stream, int kind, int B, int n, in
   return kls_grad_launch((hipStream_t)stream, true, kind, B, n, d, Xb, lengthscales, W, gls, work);
 }
 
-int evr_kernel_matrix_members(void* stream, int kind, int B, int n, int d, const double* Xb, const int* nvalid,
-                              const double* lengthscales, const double* diag_add, double* K) {
+// evr_kernel_matrix_members[_scaled]: outputscale nullptr is the unscaled form (scale 1.0, as before)
+static int kernel_matrix_members_launch(void* stream, int kind, int B, int n, int d, const double* Xb,
+                                        const int* nvalid, const double* lengthscales, const double* outputscale,
+                                        const double* diag_add, double* K) {
   EVR_CHECK(kind >= 0 && kind <= 3, "evr_kernel_matrix_members: one kernel family 0..3, got %d", kind);
   EVR_CHECK(B >= 1 && n >= 1 && d >= 1 && d <= KMAXD && Xb && nvalid && lengthscales && K,
             "evr_kernel_matrix_members: bad arguments B=%d n=%d d=%d", B, n, d);
@@ -1229,8 +1443,8 @@ int evr_kernel_matrix_members(void* stream, int kind, int B, int n, int d, const
     const int nt = cdiv(n, KT);
     const long long tiles = (long long)nt * (nt + 1) / 2 * B;
 #define KS(DP_, K_)                                                                                               \
-  kmat_mfma_sym<DP_, K_, const int*><<<(unsigned)tiles, 256, 0, s>>>(n, d, B, Xb, none, none, lengthscales, none, \
-                                                                     diag_add, K, nvalid)
+  kmat_mfma_sym<DP_, K_, const int*><<<(unsigned)tiles, 256, 0, s>>>(n, d, B, Xb, none, none, lengthscales,       \
+                                                                     outputscale, diag_add, K, nvalid)
 #define KSD(DP_)                                \
   if (kind == RBF) KS(DP_, RBF);                \
   else if (kind == MATERN05) KS(DP_, MATERN05); \
@@ -1251,7 +1465,8 @@ int evr_kernel_matrix_members(void* stream, int kind, int B, int n, int d, const
   dim3 g(cdiv(n, KT), cdiv(n, 16 * ra), B);
 #define KTK(K_)                                                                                                  \
   kmat_kernel<ra, K_, const int*><<<g, 256, lds, s>>>(kind, n, n, d, Xb, none, none, Xb, none, none, lengthscales, \
-                                                      none, diag_add, K, nullptr, nullptr, nullptr, nullptr, 0, nvalid)
+                                                      outputscale, diag_add, K, nullptr, nullptr, nullptr, nullptr, 0, \
+                                                      nvalid)
   if (kind == RBF) KTK(RBF);
   else if (kind == MATERN05) KTK(MATERN05);
   else if (kind == MATERN15) KTK(MATERN15);
@@ -1259,6 +1474,18 @@ int evr_kernel_matrix_members(void* stream, int kind, int B, int n, int d, const
 #undef KTK
   EVR_LAUNCH_CHECK();
   return 0;
+}
+
+int evr_kernel_matrix_members(void* stream, int kind, int B, int n, int d, const double* Xb, const int* nvalid,
+                              const double* lengthscales, const double* diag_add, double* K) {
+  return kernel_matrix_members_launch(stream, kind, B, n, d, Xb, nvalid, lengthscales, nullptr, diag_add, K);
+}
+
+int evr_kernel_matrix_members_scaled(void* stream, int kind, int B, int n, int d, const double* Xb, const int* nvalid,
+                                     const double* lengthscales, const double* outputscale, const double* diag_add,
+                                     double* K) {
+  EVR_CHECK(outputscale, "evr_kernel_matrix_members_scaled: outputscale required");
+  return kernel_matrix_members_launch(stream, kind, B, n, d, Xb, nvalid, lengthscales, outputscale, diag_add, K);
 }
 
 

@@ -149,14 +149,24 @@ __global__ __launch_bounds__(256) void mll_matvec(int n, const double* __restric
 // r = Y - constant (one launch: the constant comes straight from the host buffer, one read
 // per wave since a wave's rows share a member when n >= 64)
 // Member plans (nvalid != nullptr): r = 0 on a member's padded rows i >= nvalid[b].
+// Scaled plans (one trailing argument more, the outputscale buffer): hx carries the outputscales
+// (B) between the constants and the sequence number.  The unscaled instantiation has an empty
+// pack: its arguments and its code are what they were.
+__device__ __forceinline__ void mll_copy_os(int, int, int, const double*) {}
+__device__ __forceinline__ void mll_copy_os(int i, int B, int d, const double* hx, double* os) {
+  if (i < B) os[i] = hx[B * d + 2 * B + i];
+}
+template <class... OS>
 __global__ void mll_copy_in(int B, int n, int d, const double* hx, const double* __restrict__ Y, double* ls,
-                            double* noise, double* cst, double* __restrict__ r, const int* __restrict__ nvalid) {
+                            double* noise, double* cst, double* __restrict__ r, const int* __restrict__ nvalid,
+                            OS... os) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B * d) ls[i] = hx[i];
   if (i < B) {
     noise[i] = hx[B * d + i];
     cst[i] = hx[B * d + B + i];
   }
+  mll_copy_os(i, B, d, hx, os...);
   if (i < B * n) {
     const int b = i / n;
     const double v = Y[i] - hx[B * d + B + b];
@@ -169,6 +179,9 @@ __global__ void mll_copy_in(int B, int n, int d, const double* hx, const double*
 // Member plans (nvalid != nullptr): the identity block of a member's padded rows adds exactly
 // its size n - nvalid[b] to ||L^-1||_F^2 = tr K^-1, taken off here; the other four terms get
 // exact zeros from the padding (log 1, r = alpha = 0).
+// Scaled plans: gls holds [gls (B x d) | gos (B)] (evr_kernel_hyper_grad's output), copied as it
+// is, so info and the completion word sit B doubles further; hx's sequence number likewise.
+template <bool SCALED>
 __global__ void mll_copy_out(int B, int d, int nch, const double* __restrict__ part, const double* __restrict__ gls,
                              const int* __restrict__ info, const double* hx, double* hout, int n,
                              const int* __restrict__ nvalid) {
@@ -189,14 +202,15 @@ __global__ void mll_copy_out(int B, int d, int nch, const double* __restrict__ p
     if (nvalid && q == 2) s -= (double)(n - nvalid[b]);
     hout[e] = q == 0 ? 2.0 * s : s;
   }
-  for (int i = t; i < B * d; i += blockDim.x) hout[B * 5 + i] = gls[i];
-  for (int i = t; i < B; i += blockDim.x) hout[B * 5 + B * d + i] = (double)info[i];
+  const int ng = SCALED ? B * (d + 1) : B * d;   // gradient pieces
+  for (int i = t; i < ng; i += blockDim.x) hout[B * 5 + i] = gls[i];
+  for (int i = t; i < B; i += blockDim.x) hout[B * 5 + ng + i] = (double)info[i];
   __threadfence_system();
   __syncthreads();
   if (t == 0) {
-    const unsigned long long seq = *(volatile const unsigned long long*)(hx + B * d + 2 * B);
+    const unsigned long long seq = *(volatile const unsigned long long*)(hx + B * d + (SCALED ? 3 : 2) * B);
     __threadfence_system();
-    *(volatile unsigned long long*)(hout + B * 5 + B * d + B) = seq;
+    *(volatile unsigned long long*)(hout + B * 5 + ng + B) = seq;
   }
 }
 
@@ -206,10 +220,12 @@ using namespace evr;
 
 struct evr_mll_plan {
   int kind, B, n, d;
+  int scaled;          // k = outputscale * k_base: one hyperparameter and one gradient piece more
   const double* Xn;    // shared inputs (n x d), or the members' (B x n x d) when nvalid is set
   int* nvalid;         // member plans: real rows per member (device), else nullptr
   int* nvalid_h;       // its host copy
   double *Y, *ls, *noise, *cst, *K, *L, *Linv, *Dinv, *T, *r, *v, *alpha, *gls, *gw, *part, *jit0;
+  double* os;          // scaled plans: the outputscales (B), else nullptr
   int* info;
   double *hx, *hout;
   hipGraph_t graph;
@@ -219,13 +235,20 @@ struct evr_mll_plan {
 
 static int mll_chain(hipStream_t s, evr_mll_plan* p, const double* dhx, double* dhout) {
   const int B = p->B, n = p->n, d = p->d;
-  mll_copy_in<<<cdiv(std::max(B * d + B, B * n), 256), 256, 0, s>>>(B, n, d, dhx, p->Y, p->ls, p->noise, p->cst,
-                                                                       p->r, p->nvalid);
+  if (p->scaled)
+    mll_copy_in<<<cdiv(std::max(B * d + B, B * n), 256), 256, 0, s>>>(B, n, d, dhx, p->Y, p->ls, p->noise, p->cst,
+                                                                         p->r, p->nvalid, p->os);
+  else
+    mll_copy_in<<<cdiv(std::max(B * d + B, B * n), 256), 256, 0, s>>>(B, n, d, dhx, p->Y, p->ls, p->noise, p->cst,
+                                                                         p->r, p->nvalid);
   EVR_LAUNCH_CHECK();
-  if (p->nvalid) {
+  if (p->nvalid && p->scaled) {
+    if (int rc = evr_kernel_matrix_members_scaled(s, p->kind, B, n, d, p->Xn, p->nvalid, p->ls, p->os, p->noise, p->K))
+      return rc;
+  } else if (p->nvalid) {
     if (int rc = evr_kernel_matrix_members(s, p->kind, B, n, d, p->Xn, p->nvalid, p->ls, p->noise, p->K)) return rc;
   } else if (int rc = evr_kernel_matrix(s, p->kind, B, n, n, d, p->Xn, nullptr, nullptr, p->Xn, nullptr, nullptr,
-                                        p->ls, nullptr, p->noise, p->K))
+                                        p->ls, p->os, p->noise, p->K))
     return rc;
   if (int rc = chol_inverse_attempt(s, B, n, p->K, p->L, p->Linv, p->Dinv, p->T, p->jit0, p->info)) return rc;
   double* W = p->K;   // K was consumed by the factorisation
@@ -240,12 +263,21 @@ static int mll_chain(hipStream_t s, evr_mll_plan* p, const double* dhx, double* 
     else mll_w_kernel<false><<<lower * B, 256, 0, s>>>(n, B, p->Linv, p->alpha, W);
     EVR_LAUNCH_CHECK();
   }
-  if (p->nvalid) {
+  if (p->scaled) {   // [gls | gos] in one pass over W
+    if (p->nvalid) {
+      if (int rc = evr_kernel_hyper_grad_members(s, p->kind, B, n, d, p->Xn, p->nvalid, p->ls, p->os, W, p->gls, p->gw))
+        return rc;
+    } else if (int rc = evr_kernel_hyper_grad(s, p->kind, B, n, d, p->Xn, p->ls, p->os, W, p->gls, p->gw))
+      return rc;
+  } else if (p->nvalid) {
     if (int rc = evr_kernel_lengthscale_grad_members(s, p->kind, B, n, d, p->Xn, p->ls, W, p->gls, p->gw)) return rc;
   } else if (int rc = evr_kernel_lengthscale_grad(s, p->kind, B, n, d, p->Xn, p->ls, W, p->gls, p->gw))
     return rc;
   if (int rc = mll_terms_partials(s, B, n, p->L, p->Linv, p->r, p->alpha, p->part)) return rc;
-  mll_copy_out<<<1, 256, 0, s>>>(B, d, mll_terms_chunks(), p->part, p->gls, p->info, dhx, dhout, n, p->nvalid);
+  if (p->scaled)
+    mll_copy_out<true><<<1, 256, 0, s>>>(B, d, mll_terms_chunks(), p->part, p->gls, p->info, dhx, dhout, n, p->nvalid);
+  else
+    mll_copy_out<false><<<1, 256, 0, s>>>(B, d, mll_terms_chunks(), p->part, p->gls, p->info, dhx, dhout, n, p->nvalid);
   EVR_LAUNCH_CHECK();
   return 0;
 }
@@ -255,7 +287,7 @@ static void mll_free(evr_mll_plan* p) {
   if (p->exec) (void)hipGraphExecDestroy(p->exec);
   if (p->graph) (void)hipGraphDestroy(p->graph);
   double* bufs[] = {p->Y, p->ls, p->noise, p->cst, p->K, p->L, p->Linv, p->Dinv, p->T, p->r, p->v, p->alpha,
-                    p->gls, p->gw, p->part, p->jit0};
+                    p->gls, p->gw, p->part, p->jit0, p->os};
   for (double* b : bufs)
     if (b) (void)hipFree(b);
   if (p->info) (void)hipFree(p->info);
@@ -267,9 +299,9 @@ static void mll_free(evr_mll_plan* p) {
 }
 
 // evr_mll_plan_create (nvalid == nullptr: Xn n x d, shared) and evr_mll_plan_create_members
-// (nvalid: B host counts in 1..n; Xn B x n x d)
+// (nvalid: B host counts in 1..n; Xn B x n x d); scaled: the _scaled forms
 static int mll_plan_create(void* stream, int kind, int B, int n, int d, const double* Xn, const double* Y,
-                           const int* nvalid, evr_mll_plan** out) {
+                           const int* nvalid, bool scaled, evr_mll_plan** out) {
   EVR_CHECK(out && Xn && Y && B >= 1 && n >= 1 && d >= 1 && kind >= 0 && kind <= 3,
             "evr_mll_plan_create: bad arguments");
   for (int b = 0; nvalid && b < B; ++b)
@@ -282,7 +314,9 @@ static int mll_plan_create(void* stream, int kind, int B, int n, int d, const do
   p->B = B;
   p->n = n;
   p->d = d;
+  p->scaled = scaled ? 1 : 0;
   p->Xn = Xn;
+  const int sc = p->scaled;   // doubles per member more in hx and in hout, columns more in the row partials
   const size_t nn = (size_t)n * n;
   struct {
     double** ptr;
@@ -291,9 +325,10 @@ static int mll_plan_create(void* stream, int kind, int B, int n, int d, const do
               {&p->cst, (size_t)B},     {&p->K, B * nn},          {&p->L, B * nn},
               {&p->Linv, B * nn},       {&p->Dinv, chol_inverse_dinv_doubles(B, n)},
               {&p->T, (size_t)B * 64 * n}, {&p->r, (size_t)B * n}, {&p->v, (size_t)B * n},
-              {&p->alpha, (size_t)B * n}, {&p->gls, (size_t)B * d}, {&p->gw, (size_t)B * n * d},
-              {&p->part, mll_terms_part_doubles(B)}, {&p->jit0, (size_t)B}};
+              {&p->alpha, (size_t)B * n}, {&p->gls, (size_t)B * (d + sc)}, {&p->gw, (size_t)B * n * (d + sc)},
+              {&p->part, mll_terms_part_doubles(B)}, {&p->jit0, (size_t)B}, {&p->os, (size_t)B}};
   for (auto& q : need) {
+    if (q.ptr == &p->os && !sc) continue;
     if (hipMalloc((void**)q.ptr, sizeof(double) * std::max<size_t>(q.count, 1)) != hipSuccess) {
       mll_free(p);
       EVR_CHECK(false, "evr_mll_plan_create: device allocation failed");
@@ -309,15 +344,15 @@ static int mll_plan_create(void* stream, int kind, int B, int n, int d, const do
     std::memcpy(p->nvalid_h, nvalid, sizeof(int) * B);
   }
   if (hipMalloc((void**)&p->info, sizeof(int) * B) != hipSuccess ||
-      hipHostMalloc((void**)&p->hx, sizeof(double) * ((size_t)B * (d + 2) + 1),
+      hipHostMalloc((void**)&p->hx, sizeof(double) * ((size_t)B * (d + 2 + sc) + 1),
                     hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostMalloc((void**)&p->hout, sizeof(double) * ((size_t)B * (5 + d + 1) + 1),
+      hipHostMalloc((void**)&p->hout, sizeof(double) * ((size_t)B * (5 + d + sc + 1) + 1),
                     hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     mll_free(p);
     EVR_CHECK(false, "evr_mll_plan_create: allocation failed");
   }
-  std::memset(p->hx, 0, sizeof(double) * ((size_t)B * (d + 2) + 1));
-  std::memset(p->hout, 0, sizeof(double) * ((size_t)B * (5 + d + 1) + 1));
+  std::memset(p->hx, 0, sizeof(double) * ((size_t)B * (d + 2 + sc) + 1));
+  std::memset(p->hout, 0, sizeof(double) * ((size_t)B * (5 + d + sc + 1) + 1));
   hipStream_t s = (hipStream_t)stream;
   int rc = 0;
   if (hipMemcpyAsync(p->Y, Y, sizeof(double) * B * n, hipMemcpyDeviceToDevice, s) != hipSuccess ||
@@ -356,19 +391,30 @@ extern "C" {
 
 int evr_mll_plan_create(void* stream, int kind, int B, int n, int d, const double* Xn, const double* Y,
                         evr_mll_plan** out) {
-  return mll_plan_create(stream, kind, B, n, d, Xn, Y, nullptr, out);
+  return mll_plan_create(stream, kind, B, n, d, Xn, Y, nullptr, false, out);
+}
+
+int evr_mll_plan_create_scaled(void* stream, int kind, int B, int n, int d, const double* Xn, const double* Y,
+                               evr_mll_plan** out) {
+  return mll_plan_create(stream, kind, B, n, d, Xn, Y, nullptr, true, out);
+}
+
+int evr_mll_plan_create_scaled_members(void* stream, int kind, int B, int n, int d, const double* Xb, const double* Y,
+                                       const int* nvalid, evr_mll_plan** out) {
+  EVR_CHECK(nvalid, "evr_mll_plan_create_scaled_members: nvalid required");
+  return mll_plan_create(stream, kind, B, n, d, Xb, Y, nvalid, true, out);
 }
 
 int evr_mll_plan_create_members(void* stream, int kind, int B, int n, int d, const double* Xb, const double* Y,
                                 const int* nvalid, evr_mll_plan** out) {
   EVR_CHECK(nvalid, "evr_mll_plan_create_members: nvalid required");
-  return mll_plan_create(stream, kind, B, n, d, Xb, Y, nvalid, out);
+  return mll_plan_create(stream, kind, B, n, d, Xb, Y, nvalid, false, out);
 }
 
 int evr_mll_plan_eval(void* stream, evr_mll_plan* p, const double* params, double* out) {
   EVR_CHECK(p && params && out, "evr_mll_plan_eval: bad arguments");
   const int B = p->B, d = p->d;
-  const size_t nin = (size_t)B * (d + 2), nout = (size_t)B * (5 + d + 1);
+  const size_t nin = (size_t)B * (d + 2 + p->scaled), nout = (size_t)B * (5 + d + p->scaled + 1);
   hipStream_t s = (hipStream_t)stream;
   std::memcpy(p->hx, params, sizeof(double) * nin);
   const unsigned long long seq = ++p->seq;
@@ -445,8 +491,11 @@ double softplus(double v) {   // numpy logaddexp(0, v)
 // fit_gpytorch_mll's closure does) from the plan's terms (logdet, r.alpha, tr K^-1, sum alpha,
 // sum alpha^2) and lengthscale-gradient pieces gls; ls = softplus(raw).  Shared by the native
 // round driver and gp.MLLBatch (evr_mll_assemble), so both drivers see the same bits.
+// Scaled form (gos != nullptr): x has one entry more, the raw outputscale (sigma^2 = softplus(raw),
+// last), prior three more (the outputscale prior, evaluated on sigma^2), and gos[0] =
+// sum_ij W_ij k_base_ij is the gradient piece of sigma^2.
 void mll_assemble_one(int n, int d, const double* prior, const double* xb, const double* t, const double* gls,
-                      double* llo, double* gout) {
+                      const double* gos, double* llo, double* gout) {
   const int lf = (int)prior[0], nzf = (int)prior[3];
   const double logdet = t[0], quad = t[1], trKinv = t[2], sum_a = t[3], sum_a2 = t[4];
   double ll = -0.5 * quad - 0.5 * logdet - 0.5 * n * std::log(2.0 * M_PI);
@@ -470,6 +519,16 @@ void mll_assemble_one(int n, int d, const double* prior, const double* xb, const
     if (lf) dl += prior_dlogpdf(lf, prior[1], prior[2], lsj);
     gout[2 + j] = dl * (1.0 / (1.0 + std::exp(-xb[2 + j]))) / n;
   }
+  if (gos) {
+    const int of = (int)prior[6];
+    const double raw = xb[2 + d], os = softplus(raw);
+    double dos = 0.5 * gos[0];
+    if (of) {
+      ll += prior_logpdf(of, prior[7], prior[8], os);
+      dos += prior_dlogpdf(of, prior[7], prior[8], os);
+    }
+    gout[2 + d] = dos * (1.0 / (1.0 + std::exp(-raw))) / n;
+  }
   *llo = ll / n;
 }
 }  // namespace
@@ -480,8 +539,31 @@ int evr_mll_assemble(int B, int n, int d, const double* prior, const double* x, 
                      const double* gls, double* ll, double* g) {
   EVR_CHECK(B >= 0 && n >= 1 && d >= 1 && prior && x && terms && gls && ll && g, "evr_mll_assemble: bad arguments");
   for (int b = 0; b < B; ++b)
-    mll_assemble_one(n, d, prior, x + (size_t)b * (d + 2), terms + (size_t)b * 5, gls + (size_t)b * d, ll + b,
+    mll_assemble_one(n, d, prior, x + (size_t)b * (d + 2), terms + (size_t)b * 5, gls + (size_t)b * d, nullptr, ll + b,
                      g + (size_t)b * (d + 2));
+  return 0;
+}
+
+int evr_mll_assemble_scaled(int B, int n, int d, const double* prior, const double* x, const double* terms,
+                            const double* gls, const double* gos, double* ll, double* g) {
+  EVR_CHECK(B >= 0 && n >= 1 && d >= 1 && prior && x && terms && gls && gos && ll && g,
+            "evr_mll_assemble_scaled: bad arguments");
+  for (int b = 0; b < B; ++b)
+    mll_assemble_one(n, d, prior, x + (size_t)b * (d + 3), terms + (size_t)b * 5, gls + (size_t)b * d, gos + b, ll + b,
+                     g + (size_t)b * (d + 3));
+  return 0;
+}
+
+int evr_mll_assemble_scaled_members(int B, const int* nvalid, int d, const double* prior, const double* x,
+                                    const double* terms, const double* gls, const double* gos, double* ll,
+                                    double* g) {
+  EVR_CHECK(B >= 0 && nvalid && d >= 1 && prior && x && terms && gls && gos && ll && g,
+            "evr_mll_assemble_scaled_members: bad arguments");
+  for (int b = 0; b < B; ++b) {
+    EVR_CHECK(nvalid[b] >= 1, "evr_mll_assemble_scaled_members: nvalid[%d] = %d", b, nvalid[b]);
+    mll_assemble_one(nvalid[b], d, prior, x + (size_t)b * (d + 3), terms + (size_t)b * 5, gls + (size_t)b * d, gos + b,
+                     ll + b, g + (size_t)b * (d + 3));
+  }
   return 0;
 }
 
@@ -491,8 +573,8 @@ int evr_mll_assemble_members(int B, const int* nvalid, int d, const double* prio
             "evr_mll_assemble_members: bad arguments");
   for (int b = 0; b < B; ++b) {
     EVR_CHECK(nvalid[b] >= 1, "evr_mll_assemble_members: nvalid[%d] = %d", b, nvalid[b]);
-    mll_assemble_one(nvalid[b], d, prior, x + (size_t)b * (d + 2), terms + (size_t)b * 5, gls + (size_t)b * d, ll + b,
-                     g + (size_t)b * (d + 2));
+    mll_assemble_one(nvalid[b], d, prior, x + (size_t)b * (d + 2), terms + (size_t)b * 5, gls + (size_t)b * d, nullptr,
+                     ll + b, g + (size_t)b * (d + 2));
   }
   return 0;
 }
@@ -502,8 +584,8 @@ int evr_mll_fit_rounds(void* stream, evr_mll_plan* p, void** runs, int* task, do
                        int* pending) {
   EVR_CHECK(p && runs && task && x && f && g && nit && nfev && status && prior && params && pending,
             "evr_mll_fit_rounds: bad arguments");
-  const int B = p->B, d = p->d, n = p->n, nx = d + 2;
-  std::vector<double> out((size_t)B * (5 + d + 1)), gb(nx);
+  const int B = p->B, d = p->d, n = p->n, sc = p->scaled, nx = d + 2 + sc;
+  std::vector<double> out((size_t)B * (5 + d + sc + 1)), gb(nx);
   *pending = 0;
   for (;;) {
     bool any = false;
@@ -514,12 +596,14 @@ int evr_mll_fit_rounds(void* stream, evr_mll_plan* p, void** runs, int* task, do
       for (int j = 0; j < d; ++j) params[(size_t)b * d + j] = softplus(xb[2 + j]);
       params[(size_t)B * d + b] = xb[0];
       params[(size_t)B * d + B + b] = xb[1];
+      if (sc) params[(size_t)B * d + 2 * B + b] = softplus(xb[2 + d]);
     }
     if (!any) return 0;
     if (int rc = evr_mll_plan_eval(stream, p, params, out.data())) return rc;
     const double* terms = out.data();
     const double* gls = terms + (size_t)5 * B;
-    const double* info = gls + (size_t)B * d;
+    const double* gos = gls + (size_t)B * d;          // scaled plans: [gls | gos | info]
+    const double* info = gls + (size_t)B * (d + sc);
     for (int b = 0; b < B; ++b) {
       if (task[b] != EVR_LBFGSB_FG) continue;
       bool ok = info[b] == 0.0;
@@ -535,7 +619,7 @@ int evr_mll_fit_rounds(void* stream, evr_mll_plan* p, void** runs, int* task, do
       double llb;
       // a member plan's member is scaled by its own size
       mll_assemble_one(p->nvalid_h ? p->nvalid_h[b] : n, d, prior, xb, terms + (size_t)b * 5, gls + (size_t)b * d,
-                       &llb, gb.data());
+                       sc ? gos + b : nullptr, &llb, gb.data());
       // minimise -MLL / n
       f[b] = -llb;
       for (int j = 0; j < nx; ++j) g[(size_t)b * nx + j] = -gb[j];

@@ -9,3 +9,6 @@ from .models import (ActiveLearningStrategy, AdditiveSoboStrategy, AnyActiveLear
                      QehviStrategy, QnehviStrategy, QparegoStrategy, RandomStrategy, RBFKernel, ScalerEnum, SingleTaskGPSurrogate,
                      SoboStrategy, MoboStrategy, qEHVI, qEI, qLogEHVI, qLogEI, qLogNEHVI, qLogNEI, qNEHVI,
                      qNegIntPosVar, qNEI, qPI, qSR, qUCB)
+from .models import (AnyKernel, HVARFNER_LENGTHSCALE_PRIOR, HVARFNER_NOISE_PRIOR, MBO_LENGTHCALE_PRIOR, MBO_NOISE_PRIOR,
+                     MBO_OUTPUTSCALE_PRIOR, ScaleKernel, THREESIX_LENGTHSCALE_PRIOR, THREESIX_NOISE_PRIOR,
+                     THREESIX_SCALE_PRIOR)

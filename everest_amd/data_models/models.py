@@ -114,7 +114,22 @@ class MaternKernel(BaseModel):
         return nu
 
 
-AnyKernel = Annotated[Union[RBFKernel, MaternKernel], Field(discriminator="type")]
+# the stationary kernels of the device GP (RBF / Matérn ARD)
+StationaryKernel = Annotated[Union[RBFKernel, MaternKernel], Field(discriminator="type")]
+
+
+class ScaleKernel(BaseModel):
+    """bofire/data_models/kernels/aggregation.py:45-58 around the two stationary kernels:
+    k = outputscale * base_kernel, the outputscale fitted (softplus of a raw parameter) under
+    ``outputscale_prior``.  Any other base kernel (dot-product, Hamming, a nested ScaleKernel,
+    sums and products) is a validation error here."""
+    type: Literal["ScaleKernel"] = "ScaleKernel"
+    base_kernel: StationaryKernel
+    outputscale_prior: Optional[Annotated[Union[GammaPrior, NormalPrior, LogNormalPrior],
+                                          Field(discriminator="type")]] = None
+
+
+AnyKernel = Annotated[Union[RBFKernel, MaternKernel, ScaleKernel], Field(discriminator="type")]
 
 
 class LinearKernel(BaseModel):
@@ -147,6 +162,22 @@ def THREESIX_LENGTHSCALE_PRIOR():  # bofire/data_models/priors/api.py:30-32
 
 def THREESIX_NOISE_PRIOR():
     return GammaPrior(concentration=1.1, rate=0.05)
+
+
+def THREESIX_SCALE_PRIOR():
+    return GammaPrior(concentration=2.0, rate=0.15)
+
+
+def MBO_LENGTHCALE_PRIOR():  # bofire/data_models/priors/api.py:38-40 (the reference's spelling)
+    return GammaPrior(concentration=2.0, rate=0.2)
+
+
+def MBO_NOISE_PRIOR():
+    return GammaPrior(concentration=2.0, rate=4.0)
+
+
+def MBO_OUTPUTSCALE_PRIOR():
+    return GammaPrior(concentration=2.0, rate=4.0)
 
 
 # ---------------------------------------------------------------------------------------
@@ -197,7 +228,7 @@ class MixedSingleTaskGPSurrogate(BaseModel):
     dump: Optional[str] = None
     scaler: ScalerEnum = ScalerEnum.NORMALIZE
     output_scaler: ScalerEnum = ScalerEnum.STANDARDIZE
-    continuous_kernel: AnyKernel = Field(default_factory=lambda: MaternKernel(
+    continuous_kernel: StationaryKernel = Field(default_factory=lambda: MaternKernel(
         ard=True, nu=2.5, lengthscale_prior=THREESIX_LENGTHSCALE_PRIOR()))
     categorical_kernel: HammingDistanceKernel = Field(default_factory=lambda: HammingDistanceKernel(ard=True))
     noise_prior: AnyPrior = Field(default_factory=THREESIX_NOISE_PRIOR)

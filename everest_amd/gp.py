@@ -132,6 +132,21 @@ class GPHyper:
     constant: float
     y_mean: float
     y_std: float
+    outputscale: Optional[float] = None   # sigma^2 of k = sigma^2 k_base (ScaleKernel); None: no scale
+
+
+def fold_outputscale(h: GPHyper) -> GPHyper:
+    """The unscaled GP that is exactly the scaled one: a GP with (sigma^2, noise s^2, constant c,
+    y_std) on the standardised targets is the GP with kernel k_base, noise s^2 / sigma^2, constant
+    c / sigma and y_std sigma (divide the standardised targets by sigma) — the same mean, variance,
+    observation noise and joint samples in physical units.  Everything downstream of the fit
+    (GPBatch, the posterior, the acquisition chains) takes this form."""
+    if h.outputscale is None:
+        return h
+    s2 = float(h.outputscale)
+    s = math.sqrt(s2)
+    return GPHyper(lengthscale=h.lengthscale, noise=h.noise / s2, constant=h.constant / s, y_mean=h.y_mean,
+                   y_std=h.y_std * s)
 
 
 class GPBatch:
@@ -227,25 +242,35 @@ class GPBatch:
 # ---------------------------------------------------------------------------------------
 class MLLEvaluator:
     """Exact MLL / n with hyperpriors for one GP on device; raw parameter vector
-    x = [noise, constant, raw_lengthscale(d)] (BoTorch bounds: noise >= 1e-4)."""
+    x = [noise, constant, raw_lengthscale(d)] (BoTorch bounds: noise >= 1e-4).  Scaled
+    (``scaled`` or an ``outputscale_prior``): k = sigma^2 k_base, sigma^2 = softplus(raw) one entry
+    more at the end of x, its prior evaluated on sigma^2."""
 
     def __init__(self, Xn: torch.Tensor, y_std_space: np.ndarray, kind: int,
-                 ls_prior: Optional[Tuple[float, float]], noise_prior: Optional[Tuple[float, float]]):
+                 ls_prior: Optional[Tuple[float, float]], noise_prior: Optional[Tuple[float, float]],
+                 outputscale_prior=None, scaled: bool = False):
         self.Xn = Xn.contiguous()
         self.n, self.d = Xn.shape
         self.kind = kind
         self.y = np.asarray(y_std_space, dtype=np.float64)
         self.ls_prior = _prior(ls_prior)
         self.noise_prior = _prior(noise_prior)
+        self.os_prior = _prior(outputscale_prior)
+        self.scaled = bool(scaled) or self.os_prior is not None
         self.dev = Xn.device
 
     def __call__(self, x: np.ndarray):
         n, d = self.n, self.d
-        noise, const, raw = float(x[0]), float(x[1]), np.asarray(x[2:], dtype=np.float64)
+        noise, const, raw = float(x[0]), float(x[1]), np.asarray(x[2:2 + d], dtype=np.float64)
         ls = softplus_np(raw)
         dev = self.dev
         ls_t = torch.as_tensor(ls[None, :], device=dev)
-        Ky = ops.kernel_matrix(self.Xn, self.Xn, ls_t, self.kind,
+        os_t = None
+        if self.scaled:
+            raw_os = float(x[2 + d])
+            os_ = float(softplus_np(raw_os))
+            os_t = torch.tensor([os_], dtype=torch.float64, device=dev)
+        Ky = ops.kernel_matrix(self.Xn, self.Xn, ls_t, self.kind, outputscale=os_t,
                                diag_add=torch.tensor([noise], dtype=torch.float64, device=dev))
         L, Linv, _, _ = ops.cholesky_inverse(Ky, 1e-8, 3)
         r = torch.as_tensor((self.y - const)[None, :, None], device=dev)
@@ -253,7 +278,11 @@ class MLLEvaluator:
         alpha = ops.gemm(Linv, v, transA=True)                       # 1 x n x 1
         W = ops.gemm(alpha, alpha, transB=True)                      # alpha alpha^T
         ops.gemm(Linv, Linv, transA=True, alpha=-1.0, beta=1.0, out=W)   # - K^-1
-        gls = ops.kernel_lengthscale_grad(self.Xn, ls_t, W, self.kind)  # 1 x d
+        if self.scaled:
+            gls, gos = ops.kernel_hyper_grad(self.Xn, ls_t, os_t, W, self.kind)   # 1 x d, 1
+            gos = float(gos.cpu().numpy()[0])
+        else:
+            gls = ops.kernel_lengthscale_grad(self.Xn, ls_t, W, self.kind)  # 1 x d
         terms = ops.mll_terms(L, Linv, r[..., 0].contiguous(), alpha[..., 0].contiguous())
         terms = terms.cpu().numpy()[0]
         gls = gls.cpu().numpy()[0]
@@ -269,8 +298,30 @@ class MLLEvaluator:
             ll += float(prior_logpdf_np(self.noise_prior, noise))
             d_noise += float(prior_dlogpdf_np(self.noise_prior, noise))
         d_raw = d_ls * sigmoid_np(raw)
+        if self.scaled:
+            d_os = 0.5 * gos
+            if self.os_prior is not None:
+                ll += float(prior_logpdf_np(self.os_prior, os_))
+                d_os += float(prior_dlogpdf_np(self.os_prior, os_))
+            d_raw = np.concatenate([d_raw, [d_os * float(sigmoid_np(raw_os))]])
         g = np.concatenate([[d_noise, d_const], d_raw]) / n
         return ll / n, g
+
+
+# floor of a resampled outputscale: a NormalPrior's draw (taken in absolute value, as the other
+# resamples are) can land at or next to 0, whose inverse softplus is -inf
+MIN_RESAMPLED_OUTPUTSCALE = 1e-6
+
+
+def outputscale_restart_raw(os_prior, rng) -> float:
+    """The raw outputscale a fit restarts from after NotPSDError: a draw from its prior (clamped to
+    MIN_RESAMPLED_OUTPUTSCALE, as the noise draw is clamped to its bound) through the inverse
+    softplus; without a prior the start value, raw 0."""
+    osp = _prior(os_prior)
+    if osp is None:
+        return 0.0
+    v = max(float(prior_sample_np(osp, rng, 1)[0]), MIN_RESAMPLED_OUTPUTSCALE)
+    return float(v + math.log(-math.expm1(-v)))
 
 
 def noise_start(noise_prior) -> float:
@@ -288,12 +339,14 @@ def noise_start(noise_prior) -> float:
 
 def fit_single(Xn: torch.Tensor, y_raw: np.ndarray, kind: int, ls_prior, noise_prior=(-4.0, 1.0),
                max_attempts: int = 10, seed: int = 0, options: Optional[dict] = None,
-               standardize: bool = True) -> GPHyper:
+               standardize: bool = True, outputscale_prior=None, scaled: bool = False) -> GPHyper:
     """fit_gpytorch_mll restated on device kernels: minimise -mll with scipy L-BFGS-B over
     (noise >= 1e-4, constant, raw lengthscale) starting from noise = prior mode (LogNormal
     noise prior: exp(loc - scale^2)), constant 0, lengthscale softplus(0) = ln 2; on
     NotPSDError resample the hyperparameters from their priors and retry (max_attempts=10,
-    bofire/surrogates/single_task_gp.py:71)."""
+    bofire/surrogates/single_task_gp.py:71).  ``scaled`` (or an ``outputscale_prior``): the
+    ScaleKernel form, k = sigma^2 k_base with sigma^2 = softplus(raw), raw 0 at the start, the last
+    entry of x; resampled from its prior with the others, without one it goes back to its start."""
     from scipy.optimize import minimize
 
     if standardize:
@@ -302,10 +355,11 @@ def fit_single(Xn: torch.Tensor, y_raw: np.ndarray, kind: int, ls_prior, noise_p
         y_mean, y_std = 0.0, 1.0
     y = (y_raw - y_mean) / y_std
     d = Xn.shape[1]
-    lsp, nzp = _prior(ls_prior), _prior(noise_prior)
-    ev = MLLEvaluator(Xn, y, kind, lsp, nzp)
-    x0 = np.concatenate([[noise_start(nzp), 0.0], np.zeros(d)])
-    bounds = [(MIN_INFERRED_NOISE_LEVEL, None), (None, None)] + [(None, None)] * d
+    lsp, nzp, osp = _prior(ls_prior), _prior(noise_prior), _prior(outputscale_prior)
+    ev = MLLEvaluator(Xn, y, kind, lsp, nzp, osp, scaled)
+    sc = int(ev.scaled)
+    x0 = np.concatenate([[noise_start(nzp), 0.0], np.zeros(d + sc)])
+    bounds = [(MIN_INFERRED_NOISE_LEVEL, None), (None, None)] + [(None, None)] * (d + sc)
     rng = np.random.default_rng(seed)
     last_err = None
     for attempt in range(max_attempts):
@@ -313,13 +367,15 @@ def fit_single(Xn: torch.Tensor, y_raw: np.ndarray, kind: int, ls_prior, noise_p
             res = minimize(lambda x: tuple(-v for v in ev(x)), x0, jac=True, method="L-BFGS-B", bounds=bounds,
                            options=options or {})
             xv = res.x
-            return GPHyper(lengthscale=softplus_np(xv[2:]), noise=float(xv[0]), constant=float(xv[1]),
-                           y_mean=y_mean, y_std=y_std)
+            return GPHyper(lengthscale=softplus_np(xv[2:2 + d]), noise=float(xv[0]), constant=float(xv[1]),
+                           y_mean=y_mean, y_std=y_std, outputscale=float(softplus_np(xv[2 + d])) if sc else None)
         except ops.NotPSDError as e:  # sample_all_priors, then retry
             last_err = e
             ls = prior_sample_np(lsp, rng, d) if lsp else np.full(d, math.log(2.0))
             nz = max(float(prior_sample_np(nzp, rng, 1)[0]) if nzp else 1e-3, MIN_INFERRED_NOISE_LEVEL)
             x0 = np.concatenate([[nz, 0.0], np.log(np.expm1(ls))])
+            if sc:
+                x0 = np.append(x0, outputscale_restart_raw(osp, rng))
     raise RuntimeError(f"GP fit failed after {max_attempts} attempts: {last_err}")
 
 
@@ -336,15 +392,23 @@ class MLLBatch:
     Member form (``nvalid`` given): member b has its own inputs ``Xn[b]`` (Xn is B x n x d) of
     which the first ``nvalid[b]`` rows are real; the rest is padding (zeros) that the member
     kernels turn into identity rows / columns of K (include/everest_amd.h, member form), and
-    every value is that of the member's own GP on its own rows, MLL / nvalid[b]."""
+    every value is that of the member's own GP on its own rows, MLL / nvalid[b].
 
-    def __init__(self, Xn: torch.Tensor, Ys: np.ndarray, kind: int, ls_prior, noise_prior, nvalid=None):
+    Scaled form (``scaled`` or an ``outputscale_prior``): k = sigma^2 k_base; a member's x has one
+    entry more, the raw outputscale (last), and the chain, the plan and the assembly are the
+    scaled ones (evr_kernel_hyper_grad, evr_mll_plan_create_scaled, evr_mll_assemble_scaled)."""
+
+    def __init__(self, Xn: torch.Tensor, Ys: np.ndarray, kind: int, ls_prior, noise_prior, nvalid=None,
+                 outputscale_prior=None, scaled: bool = False):
         self.Xn = Xn.contiguous()
         self.n, self.d = Xn.shape[-2:]
         self.kind = kind
         self.Y = torch.as_tensor(np.asarray(Ys, dtype=np.float64), device=Xn.device)   # B x n (standardized)
         self.ls_prior = _prior(ls_prior)
         self.noise_prior = _prior(noise_prior)
+        self.os_prior = _prior(outputscale_prior)
+        self.scaled = bool(scaled) or self.os_prior is not None
+        self.nx = self.d + 2 + int(self.scaled)      # a member's raw vector
         self.use_plan = os.environ.get("EVR_MLL_PLAN", "1") != "0"
         self._plan = None
         self.nvalid = None
@@ -359,18 +423,25 @@ class MLLBatch:
             # 1 on a member's real rows, 0 on its padding
             self._real = (torch.arange(self.n, device=Xn.device)[None, :] < self._nvalid_t[:, None]).to(torch.float64)
 
-    def _eval_ops(self, idx, ls, noise, const):
-        """The op-by-op chain with the psd_safe_cholesky jitter ladder (host arrays)."""
+    def _eval_ops(self, idx, ls, noise, const, os_=None):
+        """The op-by-op chain with the psd_safe_cholesky jitter ladder (host arrays); ``os_``: the
+        outputscales of the scaled form (the ladder acts on sigma^2 K_base + noise I)."""
         dev = self.Xn.device
         ls_t = torch.as_tensor(ls, device=dev)
         it = torch.as_tensor(np.asarray(idx, dtype=np.int64), device=dev)
         members = self.nvalid is not None
+        os_t = torch.as_tensor(np.ascontiguousarray(os_), device=dev) if self.scaled else None
         if members:
             Xb, real = self.Xn[it].contiguous(), self._real[it]
-            Ky = ops.kernel_matrix_members(Xb, self._nvalid_t[it].contiguous(), ls_t, self.kind,
-                                           diag_add=torch.as_tensor(noise, device=dev))
+            nv_t = self._nvalid_t[it].contiguous()
+            if self.scaled:     # sigma^2 on the real block, the padding stays the identity
+                Ky = ops.kernel_matrix_members_scaled(Xb, nv_t, ls_t, os_t, self.kind,
+                                                      diag_add=torch.as_tensor(noise, device=dev))
+            else:
+                Ky = ops.kernel_matrix_members(Xb, nv_t, ls_t, self.kind, diag_add=torch.as_tensor(noise, device=dev))
         else:
-            Ky = ops.kernel_matrix(self.Xn, self.Xn, ls_t, self.kind, diag_add=torch.as_tensor(noise, device=dev))
+            Ky = ops.kernel_matrix(self.Xn, self.Xn, ls_t, self.kind, outputscale=os_t,
+                                   diag_add=torch.as_tensor(noise, device=dev))
         L, Linv, _, info = ops.cholesky_inverse(Ky, 1e-8, 3, raise_on_fail=False)
         r = self.Y[it] - torch.as_tensor(const, device=dev)[:, None]
         if members:
@@ -380,7 +451,14 @@ class MLLBatch:
         alpha = ops.gemm(Linv, v, transA=True)
         W = ops.gemm(alpha, alpha, transB=True)
         ops.gemm(Linv, Linv, transA=True, alpha=-1.0, beta=1.0, out=W)
-        if members:
+        gos = None
+        if self.scaled and members:
+            # the member kernel sums over the member's own rows and columns: the padding's share of
+            # gos (W = -1 / (1 + jitter) on its diagonal, k_base = 1) never enters
+            gls, gos = ops.kernel_hyper_grad_members(Xb, nv_t, ls_t, os_t, W, self.kind)
+        elif self.scaled:
+            gls, gos = ops.kernel_hyper_grad(self.Xn, ls_t, os_t, W, self.kind)
+        elif members:
             gls = ops.kernel_lengthscale_grad_members(Xb, ls_t, W, self.kind)
         else:
             gls = ops.kernel_lengthscale_grad(self.Xn, ls_t, W, self.kind)
@@ -392,58 +470,67 @@ class MLLBatch:
             pad = 1.0 - real
             terms[:, 0] -= 2.0 * (torch.log(L.diagonal(dim1=-2, dim2=-1)) * pad).sum(1)
             terms[:, 2] -= (Linv.diagonal(dim1=-2, dim2=-1) ** 2 * pad).sum(1)
-        return torch.cat([terms.reshape(-1), gls.reshape(-1), info.to(torch.float64)]).cpu().numpy()
+        pieces = [terms.reshape(-1), gls.reshape(-1)] + ([gos.reshape(-1)] if self.scaled else [])
+        return torch.cat(pieces + [info.to(torch.float64)]).cpu().numpy()
 
     def plan_handle(self):
         """The native MLL plan (evr_mll_plan_create[_members]), built on first use."""
         if self._plan is None:
             Bt, d = self.Y.shape[0], self.d
             h = ctypes.c_void_p()
+            sfx = "_scaled" if self.scaled else ""
             if self.nvalid is not None:
-                ops.call("evr_mll_plan_create_members", ops._stream(), int(self.kind), Bt, self.n, d,
+                ops.call(f"evr_mll_plan_create{sfx}_members", ops._stream(), int(self.kind), Bt, self.n, d,
                          self.Xn.data_ptr(), self.Y.data_ptr(), self.nvalid.ctypes.data, ctypes.byref(h))
             else:
-                ops.call("evr_mll_plan_create", ops._stream(), int(self.kind), Bt, self.n, d, self.Xn.data_ptr(),
+                ops.call(f"evr_mll_plan_create{sfx}", ops._stream(), int(self.kind), Bt, self.n, d, self.Xn.data_ptr(),
                          self.Y.data_ptr(), ctypes.byref(h))
             self._plan = h
             self._lib = _native.load()
             self._params = None
-            self._pout = np.empty(Bt * (5 + d + 1))
+            self._pout = np.empty(Bt * (5 + d + int(self.scaled) + 1))
         return self._plan
 
     def prior_spec(self) -> np.ndarray:
         """[ls family, a, b, noise family, a, b] for evr_mll_fit_rounds (family 0 none,
-        1 LogNormal, 2 Gamma, 3 Normal)."""
+        1 LogNormal, 2 Gamma, 3 Normal); the scaled form has three entries more, the outputscale
+        prior's."""
         fam = {"lognormal": 1, "gamma": 2, "normal": 3}
-        out = np.zeros(6)
-        for k, p in enumerate((self.ls_prior, self.noise_prior)):
+        out = np.zeros(9 if self.scaled else 6)
+        for k, p in enumerate((self.ls_prior, self.noise_prior) + ((self.os_prior,) if self.scaled else ())):
             if p is not None:
                 out[3 * k:3 * k + 3] = (fam[p[0]], p[1], p[2])
         return out
 
-    def _eval_plan(self, idx, ls, noise, const):
+    def _eval_plan(self, idx, ls, noise, const, os_=None):
         """All members through the native MLL plan (evr_mll_plan_eval: one graph launch);
         members outside idx keep their last parameters.  None when an active member's
         attempt-0 factor fails (the caller takes the ladder path)."""
         Bt, d = self.Y.shape[0], self.d
         self.plan_handle()
+        sc = int(self.scaled)
         if self._params is None:
-            self._params = np.empty((Bt, d + 2))
+            self._params = np.empty((Bt, d + 2 + sc))
             self._params[:, :d] = ls[0]
             self._params[:, d] = noise[0]
             self._params[:, d + 1] = const[0]
+            if sc:
+                self._params[:, d + 2] = os_[0]
         P = self._params
         for k, b in enumerate(idx):
             P[b, :d], P[b, d], P[b, d + 1] = ls[k], noise[k], const[k]
-        flat = np.concatenate([P[:, :d].reshape(-1), P[:, d], P[:, d + 1]])
+            if sc:
+                P[b, d + 2] = os_[k]
+        flat = np.concatenate([P[:, :d].reshape(-1), P[:, d], P[:, d + 1]] + ([P[:, d + 2]] if sc else []))
         _native.check(self._lib.evr_mll_plan_eval(ops._stream(), self._plan, flat.ctypes.data, self._pout.ctypes.data),
                       "evr_mll_plan_eval")
         o = self._pout
-        terms, gls, info = o[:5 * Bt].reshape(Bt, 5), o[5 * Bt:5 * Bt + Bt * d].reshape(Bt, d), o[5 * Bt + Bt * d:]
+        terms, gls = o[:5 * Bt].reshape(Bt, 5), o[5 * Bt:5 * Bt + Bt * d].reshape(Bt, d)
+        gos, info = o[5 * Bt + Bt * d:5 * Bt + Bt * (d + sc)], o[5 * Bt + Bt * (d + sc):]
         ii = np.asarray(idx, dtype=np.int64)
         if np.any(info[ii] != 0):
             return None
-        return np.concatenate([terms[ii].reshape(-1), gls[ii].reshape(-1), info[ii]])
+        return np.concatenate([terms[ii].reshape(-1), gls[ii].reshape(-1)] + ([gos[ii]] if sc else []) + [info[ii]])
 
     def __del__(self):
         h = getattr(self, "_plan", None)
@@ -457,22 +544,37 @@ class MLLBatch:
     def __call__(self, idx: Sequence[int], xs: Sequence[np.ndarray]):
         n, d = self.n, self.d
         xs = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.float64) for x in xs]))
-        noise, const, raw = xs[:, 0], xs[:, 1], xs[:, 2:]
+        sc = int(self.scaled)
+        if xs.shape[1] != self.nx:
+            raise ValueError(f"MLLBatch: raw vectors of {xs.shape[1]} entries, expected {self.nx}")
+        noise, const, raw = xs[:, 0], xs[:, 1], xs[:, 2:2 + d]
         # softplus with libm's scalar exp / log1p: the native round driver's arithmetic
         ls = np.array([[_softplus_libm(v) for v in row] for row in raw]).reshape(raw.shape)
-        host = self._eval_plan(idx, ls, noise, const) if self.use_plan else None
+        os_ = np.array([_softplus_libm(v) for v in xs[:, 2 + d]]) if sc else None
+        host = self._eval_plan(idx, ls, noise, const, os_) if self.use_plan else None
         if host is None:
-            host = self._eval_ops(idx, ls, noise, const)
+            host = self._eval_ops(idx, ls, noise, const, os_)
         B = len(idx)
         terms_h = np.ascontiguousarray(host[:5 * B].reshape(B, 5))
         gls_h = np.ascontiguousarray(host[5 * B:5 * B + B * d].reshape(B, d))
-        info_h = host[5 * B + B * d:]
+        gos_h = np.ascontiguousarray(host[5 * B + B * d:5 * B + B * (d + sc)])
+        info_h = host[5 * B + B * (d + sc):]
         # ll / n and its gradient with the priors: evr_mll_assemble, the code the native driver
         # (evr_mll_fit_rounds) runs, so both drivers take bitwise the same L-BFGS-B steps
         ll = np.empty(B)
-        g = np.empty((B, d + 2))
+        g = np.empty((B, self.nx))
         lib = _native.load()
-        if self.nvalid is not None:      # member b's own size in the -n/2 log 2 pi term and the 1 / n
+        if sc and self.nvalid is not None:
+            nv = np.ascontiguousarray(self.nvalid[np.asarray(idx, dtype=np.int64)])
+            _native.check(lib.evr_mll_assemble_scaled_members(B, nv.ctypes.data, d, self.prior_spec().ctypes.data,
+                                                              xs.ctypes.data, terms_h.ctypes.data, gls_h.ctypes.data,
+                                                              gos_h.ctypes.data, ll.ctypes.data, g.ctypes.data),
+                          "evr_mll_assemble_scaled_members")
+        elif sc:
+            _native.check(lib.evr_mll_assemble_scaled(B, n, d, self.prior_spec().ctypes.data, xs.ctypes.data,
+                                                      terms_h.ctypes.data, gls_h.ctypes.data, gos_h.ctypes.data,
+                                                      ll.ctypes.data, g.ctypes.data), "evr_mll_assemble_scaled")
+        elif self.nvalid is not None:      # member b's own size in the -n/2 log 2 pi term and the 1 / n
             nv = np.ascontiguousarray(self.nvalid[np.asarray(idx, dtype=np.int64)])
             _native.check(lib.evr_mll_assemble_members(B, nv.ctypes.data, d, self.prior_spec().ctypes.data,
                                                        xs.ctypes.data, terms_h.ctypes.data, gls_h.ctypes.data,
@@ -500,7 +602,7 @@ def _fit_rounds_native(ev: "MLLBatch", B: int, d: int, x0: np.ndarray, lb: np.nd
     from .optim import _EPS, LBFGSB_FG
 
     lib = _native.load()
-    nx = d + 2
+    nx = ev.nx       # d + 2, or d + 3 over a scaled plan
     lo = np.ascontiguousarray(lb, dtype=np.float64)
     hi = np.ascontiguousarray(ub, dtype=np.float64)
     runs = (ctypes.c_void_p * B)()
@@ -565,7 +667,7 @@ def _fit_rounds_native(ev: "MLLBatch", B: int, d: int, x0: np.ndarray, lb: np.nd
 
 def fit_batch(Xn: torch.Tensor, Y_raw: np.ndarray, kind: int, ls_prior, noise_prior=(-4.0, 1.0),
               max_attempts: int = 10, seed: int = 0, options: Optional[dict] = None,
-              standardize: bool = True) -> List[GPHyper]:
+              standardize: bool = True, outputscale_prior=None, scaled: bool = False) -> List[GPHyper]:
     """fit_single for the B columns of ``Y_raw`` (n x B) on shared inputs, in lock-step: each
     output runs its own L-BFGS-B (the native restatement of scipy's, csrc/lbfgsb.cpp; same
     start, bounds and NotPSDError retries with prior samples as fit_single), and every round
@@ -580,7 +682,7 @@ def fit_batch(Xn: torch.Tensor, Y_raw: np.ndarray, kind: int, ls_prior, noise_pr
         stats.append((ym, ys))
         Ys.append((Y_raw[:, b] - ym) / ys)
     lsp, nzp = _prior(ls_prior), _prior(noise_prior)
-    ev = MLLBatch(Xn, np.stack(Ys), kind, lsp, nzp)
+    ev = MLLBatch(Xn, np.stack(Ys), kind, lsp, nzp, outputscale_prior=outputscale_prior, scaled=scaled)
     return _fit_lockstep(ev, stats, max_attempts, seed, options)
 
 
@@ -590,7 +692,7 @@ def _fit_lockstep(ev: MLLBatch, stats, max_attempts: int, seed: int, options: Op
     from .optim import lbfgsb_steps
 
     B, d = ev.Y.shape[0], ev.d
-    lsp, nzp = ev.ls_prior, ev.noise_prior
+    lsp, nzp, osp, sc = ev.ls_prior, ev.noise_prior, ev.os_prior, int(ev.scaled)
     opts = dict(options or {})
     maxiter, maxfun = int(opts.get("maxiter", 15000)), int(opts.get("maxfun", 15000))
     if nzp is not None and nzp[0] == "lognormal":
@@ -600,8 +702,8 @@ def _fit_lockstep(ev: MLLBatch, stats, max_attempts: int, seed: int, options: Op
     else:
         noise0 = 2 * MIN_INFERRED_NOISE_LEVEL
     noise0 = max(noise0, MIN_INFERRED_NOISE_LEVEL)
-    lb = np.r_[MIN_INFERRED_NOISE_LEVEL, -np.inf, np.full(d, -np.inf)]
-    ub = np.full(d + 2, np.inf)
+    lb = np.r_[MIN_INFERRED_NOISE_LEVEL, -np.inf, np.full(d + sc, -np.inf)]
+    ub = np.full(d + 2 + sc, np.inf)
     rngs = [np.random.default_rng(seed) for _ in range(B)]
     attempts = [0] * B
 
@@ -611,19 +713,26 @@ def _fit_lockstep(ev: MLLBatch, stats, max_attempts: int, seed: int, options: Op
             raise RuntimeError(f"GP fit of output {b} failed after {max_attempts} attempts (NotPSDError)")
         ls = prior_sample_np(lsp, rngs[b], d) if lsp else np.full(d, math.log(2.0))
         nz = max(float(prior_sample_np(nzp, rngs[b], 1)[0]) if nzp else 1e-3, MIN_INFERRED_NOISE_LEVEL)
-        return np.concatenate([[nz, 0.0], np.log(np.expm1(ls))])
+        x = np.concatenate([[nz, 0.0], np.log(np.expm1(ls))])
+        if sc:    # sigma^2 from its prior with the others; without one it goes back to its start
+            x = np.append(x, outputscale_restart_raw(osp, rngs[b]))
+        return x
 
+    def hyper(b, x):
+        return GPHyper(lengthscale=softplus_np(x[2:2 + d]), noise=float(x[0]), constant=float(x[1]),
+                       y_mean=stats[b][0], y_std=stats[b][1],
+                       outputscale=float(softplus_np(x[2 + d])) if sc else None)
+
+    x_start = np.concatenate([[noise0, 0.0], np.zeros(d + sc)])
     if ev.use_plan and os.environ.get("EVR_FIT_NATIVE", "1") != "0":
-        xs = _fit_rounds_native(ev, B, d, np.concatenate([[noise0, 0.0], np.zeros(d)]), lb, ub, maxiter, maxfun,
-                                restart_x)
-        return [GPHyper(lengthscale=softplus_np(xs[b][2:]), noise=float(xs[b][0]), constant=float(xs[b][1]),
-                        y_mean=stats[b][0], y_std=stats[b][1]) for b in range(B)]
+        xs = _fit_rounds_native(ev, B, d, x_start, lb, ub, maxiter, maxfun, restart_x)
+        return [hyper(b, xs[b]) for b in range(B)]
 
     def start(x0):
         gen = lbfgsb_steps(x0, lb, ub, maxiter, maxfun)
         return gen, next(gen)
 
-    runs = {b: start(np.concatenate([[noise0, 0.0], np.zeros(d)])) for b in range(B)}
+    runs = {b: start(x_start) for b in range(B)}
     result, counts = {}, {}
     while runs:
         idx = sorted(runs)
@@ -642,8 +751,7 @@ def _fit_lockstep(ev: MLLBatch, stats, max_attempts: int, seed: int, options: Op
                 counts[b] = (stop.value.nfev, stop.value.nit)
                 del runs[b]
     LAST_FIT_STATS.update(driver="python", nfev=[counts[b][0] for b in range(B)], nit=[counts[b][1] for b in range(B)])
-    return [GPHyper(lengthscale=softplus_np(result[b][2:]), noise=float(result[b][0]), constant=float(result[b][1]),
-                    y_mean=stats[b][0], y_std=stats[b][1]) for b in range(B)]
+    return [hyper(b, result[b]) for b in range(B)]
 
 
 # ---------------------------------------------------------------------------------------
@@ -668,7 +776,8 @@ def member_chunks(B: int, n: int, d: int) -> List[range]:
 
 
 def fit_folds(Xb, Y_raw_b: np.ndarray, nvalid, kind: int, ls_prior, noise_prior, standardize: bool,
-              max_attempts: int = 10, seed: int = 0, options: Optional[dict] = None) -> List[GPHyper]:
+              max_attempts: int = 10, seed: int = 0, options: Optional[dict] = None, outputscale_prior=None,
+              scaled: bool = False) -> List[GPHyper]:
     """fit_batch for B members that each train on their own rows (the folds of
     SingleTaskGPSurrogate.cross_validate): member b has the normalised inputs ``Xb[b]``
     (B x nmax x d, device; rows >= ``nvalid[b]`` are padding and must be zeros) and the raw
@@ -696,7 +805,8 @@ def fit_folds(Xb, Y_raw_b: np.ndarray, nvalid, kind: int, ls_prior, noise_prior,
     hypers, nfev, nit, driver = [], [], [], None
     for ch in member_chunks(B, n, d):
         sl = slice(ch.start, ch.stop)
-        ev = MLLBatch(Xb[sl], Ys[sl], kind, lsp, nzp, nvalid=nvalid[sl])
+        ev = MLLBatch(Xb[sl], Ys[sl], kind, lsp, nzp, nvalid=nvalid[sl], outputscale_prior=outputscale_prior,
+                      scaled=scaled)
         hypers += _fit_lockstep(ev, stats[sl], max_attempts, seed, options)
         nfev += LAST_FIT_STATS["nfev"]
         nit += LAST_FIT_STATS["nit"]

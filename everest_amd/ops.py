@@ -144,6 +144,57 @@ def kernel_lengthscale_grad_members(Xb, lengthscales, W, kind=0) -> torch.Tensor
     return g
 
 
+def _outputscale(outputscale, B: int) -> torch.Tensor:
+    os_ = _dev(outputscale, "outputscale")
+    if tuple(os_.shape) != (B,):
+        raise ValueError(f"outputscale {tuple(os_.shape)} must hold one value per member ({B})")
+    return os_
+
+
+def kernel_hyper_grad(X, lengthscales, outputscale, W, kind=0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(gls B x d, gos B) of the scaled kernel k = outputscale k_base in one pass over W
+    (evr_kernel_hyper_grad): gls = outputscale sum W dk_base/dls, gos = sum W k_base."""
+    X, ls, W = _dev(X, "X"), _dev(lengthscales, "ls"), _dev(W, "W")
+    B, d = ls.shape
+    n = X.shape[0]
+    if tuple(W.shape) != (B, n, n) or X.shape[1] != d:
+        raise ValueError(f"kernel_hyper_grad: X {tuple(X.shape)}, ls {tuple(ls.shape)}, W {tuple(W.shape)} do not match")
+    os_ = _outputscale(outputscale, B)
+    out = torch.empty(B * (d + 1), dtype=torch.float64, device=X.device)
+    work = torch.empty(B, n, d + 1, dtype=torch.float64, device=X.device)
+    call("evr_kernel_hyper_grad", _stream(), int(kind), B, n, d, X.data_ptr(), ls.data_ptr(), os_.data_ptr(),
+         W.data_ptr(), out.data_ptr(), work.data_ptr())
+    return out[:B * d].reshape(B, d), out[B * d:]
+
+
+def kernel_hyper_grad_members(Xb, nvalid, lengthscales, outputscale, W, kind=0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """kernel_hyper_grad with member b on its own rows Xb[b, :nvalid[b]] (the sums skip the padding)."""
+    Xb, ls, nvalid = _members(Xb, lengthscales, nvalid)
+    W = _dev(W, "W")
+    B, n, d = Xb.shape
+    if tuple(W.shape) != (B, n, n):
+        raise ValueError(f"kernel_hyper_grad_members: W shape {tuple(W.shape)} != {(B, n, n)}")
+    os_ = _outputscale(outputscale, B)
+    out = torch.empty(B * (d + 1), dtype=torch.float64, device=Xb.device)
+    work = torch.empty(B, n, d + 1, dtype=torch.float64, device=Xb.device)
+    call("evr_kernel_hyper_grad_members", _stream(), int(kind), B, n, d, Xb.data_ptr(), nvalid.data_ptr(),
+         ls.data_ptr(), os_.data_ptr(), W.data_ptr(), out.data_ptr(), work.data_ptr())
+    return out[:B * d].reshape(B, d), out[B * d:]
+
+
+def kernel_matrix_members_scaled(Xb, nvalid, lengthscales, outputscale, kind: int = 0, diag_add=None) -> torch.Tensor:
+    """kernel_matrix_members with outputscale[b] on member b's real block; the padding stays the
+    identity (evr_kernel_matrix_members_scaled)."""
+    Xb, ls, nvalid = _members(Xb, lengthscales, nvalid)
+    B, n, d = Xb.shape
+    os_ = _outputscale(outputscale, B)
+    K = torch.empty(B, n, n, dtype=torch.float64, device=Xb.device)
+    dg = None if diag_add is None else _dev(diag_add, "diag_add")
+    call("evr_kernel_matrix_members_scaled", _stream(), int(kind), B, n, d, Xb.data_ptr(), nvalid.data_ptr(),
+         ls.data_ptr(), os_.data_ptr(), _p(dg), K.data_ptr())
+    return K
+
+
 # limits of the mixed-kernel entry points (include/everest_amd.h)
 MIXED_MAX_DC, MIXED_MAX_NC = 32, 8
 

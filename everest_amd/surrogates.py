@@ -28,7 +28,7 @@ from . import data_models as dm
 from .data_models.models import (CategoricalEncodingEnum, DimensionalityScaledLogNormalPrior, GammaPrior,
                                   LogNormalPrior, MaternKernel, NormalPrior, RBFKernel, ScalerEnum)
 from .diagnostics import CvResult, CvResults
-from .gp import GPBatch, GPHyper, fit_single, standardize_params
+from .gp import GPBatch, GPHyper, fit_single, fold_outputscale, standardize_params
 
 KIND_BY_NU = {0.5: 1, 1.5: 2, 2.5: 3}
 # feature types a cross-validation can be stratified by (of the reference's DiscreteInput,
@@ -100,6 +100,15 @@ def kernel_kind(kernel) -> int:
     if isinstance(kernel, MaternKernel):
         return KIND_BY_NU[kernel.nu]
     raise NotImplementedError(f"kernel {type(kernel).__name__} is out of scope for the MI355X build")
+
+
+def unwrap_scale(kernel):
+    """(base kernel, scaled, outputscale prior spec) of a SingleTaskGPSurrogate kernel: a
+    ScaleKernel gives its base kernel (family and lengthscale prior come from it) and a fitted
+    outputscale (bofire/kernels/mapper.py: gpytorch ScaleKernel(base, outputscale_prior))."""
+    if isinstance(kernel, dm.ScaleKernel):
+        return kernel.base_kernel, True, map_prior(kernel.outputscale_prior, 1)
+    return kernel, False, None
 
 
 def map_prior(prior, d: int) -> Optional[Tuple[str, float, float]]:
@@ -249,28 +258,38 @@ class SingleTaskGPSurrogate:
         """Everything the MLL fit needs: transformed inputs, bounds, targets, kernel, priors."""
         Xt = self.transform_inputs(X)
         lo, hi = self._bounds(X)
-        return dict(Xt=Xt, lo=lo, hi=hi, y=Y.values[:, 0].astype(np.float64), kind=kernel_kind(self.kernel),
-                    ls_prior=map_prior(getattr(self.kernel, "lengthscale_prior", None), Xt.shape[1]),
+        base, scaled, os_prior = unwrap_scale(self.kernel)
+        return dict(Xt=Xt, lo=lo, hi=hi, y=Y.values[:, 0].astype(np.float64), kind=kernel_kind(base),
+                    ls_prior=map_prior(getattr(base, "lengthscale_prior", None), Xt.shape[1]),
                     noise_prior=map_prior(self.noise_prior, 1),
-                    standardize=self.output_scaler == ScalerEnum.STANDARDIZE)
+                    standardize=self.output_scaler == ScalerEnum.STANDARDIZE,
+                    scaled=scaled, os_prior=os_prior)
 
     def _fit(self, X: pd.DataFrame, Y: pd.DataFrame, options: Optional[dict] = None):
         pb = self._fit_problem(X, Y)
         Xn = torch.as_tensor((pb["Xt"] - pb["lo"]) / (pb["hi"] - pb["lo"]), dtype=torch.float64, device=device())
         hyp = fit_single(Xn, pb["y"], pb["kind"], pb["ls_prior"], pb["noise_prior"], standardize=pb["standardize"],
-                         options=options)
+                         options=options, outputscale_prior=pb["os_prior"], scaled=pb["scaled"])
         self._set_state(pb["Xt"], pb["y"], pb["lo"], pb["hi"], pb["kind"], hyp)
 
     def _set_state(self, Xt, y, lo, hi, kind, hyp: GPHyper):
         self.state = dict(X=np.asarray(Xt), y=np.asarray(y), lo=np.asarray(lo), hi=np.asarray(hi), kind=int(kind),
                           lengthscale=np.asarray(hyp.lengthscale), noise=float(hyp.noise),
                           constant=float(hyp.constant), y_mean=float(hyp.y_mean), y_std=float(hyp.y_std))
+        if hyp.outputscale is not None:      # a ScaleKernel fit: sigma^2 as fitted, the others unfolded
+            self.state["outputscale"] = float(hyp.outputscale)
         self.gp = self._build_gp()
 
-    def hyper(self) -> GPHyper:
+    def fitted_hyper(self) -> GPHyper:
+        """The hyperparameters as fitted (a ScaleKernel's outputscale apart)."""
         s = self.state
         return GPHyper(lengthscale=s["lengthscale"], noise=s["noise"], constant=s["constant"], y_mean=s["y_mean"],
-                       y_std=s["y_std"])
+                       y_std=s["y_std"], outputscale=s.get("outputscale"))
+
+    def hyper(self) -> GPHyper:
+        """The device model's hyperparameters: a fitted outputscale folded into noise, constant and
+        y_std (gp.fold_outputscale: exactly the same GP), so nothing downstream knows about it."""
+        return fold_outputscale(self.fitted_hyper())
 
     def _build_gp(self) -> GPBatch:
         s = self.state
@@ -342,7 +361,7 @@ class SingleTaskGPSurrogate:
         dev = device()
         t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64), device=dev)  # noqa: E731
         hyps = fit_folds(t(Xb), Yb, [len(tr) for tr, _ in splits], pb["kind"], pb["ls_prior"], pb["noise_prior"],
-                         pb["standardize"])
+                         pb["standardize"], outputscale_prior=pb["os_prior"], scaled=pb["scaled"])
         Xall, Xn_all = t(Xt), t((Xt - lo0) / (hi0 - lo0))
         out = []
         for ch in member_chunks(B, nmax, d):
@@ -351,7 +370,7 @@ class SingleTaskGPSurrogate:
             for k, j in enumerate(ch):
                 mask[k, splits[j][0]] = True
                 lo, hi = bounds[j]
-                h = hyps[j]
+                h = fold_outputscale(hyps[j])
                 # the fold's Normalize bounds folded into its lengthscales: the stationary kernels
                 # see (x - x') / ((hi - lo) ls) only
                 folded.append(GPHyper(lengthscale=np.asarray(h.lengthscale) * ((hi - lo) / (hi0 - lo0)), noise=h.noise,
@@ -384,6 +403,8 @@ class SingleTaskGPSurrogate:
         meta = {"format": "everest_amd.SingleTaskGP/1", "kind": s["kind"], "noise": s["noise"],
                 "constant": s["constant"], "y_mean": s["y_mean"], "y_std": s["y_std"],
                 "arrays": base64.b64encode(buf.getvalue()).decode()}
+        if "outputscale" in s:       # optional key, last: a dump without a scale is what it was
+            meta["outputscale"] = s["outputscale"]
         return base64.b64encode(json.dumps(meta).encode()).decode()
 
     def loads(self, data: str):
@@ -392,7 +413,7 @@ class SingleTaskGPSurrogate:
             raise ValueError("unknown surrogate dump format (BoTorch pickles cannot be loaded without BoTorch)")
         arr = np.load(io.BytesIO(base64.b64decode(meta["arrays"])), allow_pickle=False)
         hyp = GPHyper(lengthscale=arr["lengthscale"], noise=meta["noise"], constant=meta["constant"],
-                      y_mean=meta["y_mean"], y_std=meta["y_std"])
+                      y_mean=meta["y_mean"], y_std=meta["y_std"], outputscale=meta.get("outputscale"))
         self._set_state(arr["X"], arr["y"], arr["lo"], arr["hi"], meta["kind"], hyp)
 
 
@@ -726,7 +747,7 @@ class BotorchSurrogates:
             groups = {}
             for s, pb in probs:
                 key = (pb["Xt"].shape, pb["Xt"].tobytes(), pb["lo"].tobytes(), pb["hi"].tobytes(), pb["kind"],
-                       pb["ls_prior"], pb["noise_prior"], pb["standardize"])
+                       pb["ls_prior"], pb["noise_prior"], pb["standardize"], pb["scaled"], pb["os_prior"])
                 groups.setdefault(key, []).append((s, pb))
             rest = []
             for members in groups.values():
@@ -737,7 +758,8 @@ class BotorchSurrogates:
                 Xn = torch.as_tensor((pb0["Xt"] - pb0["lo"]) / (pb0["hi"] - pb0["lo"]), dtype=torch.float64,
                                      device=device())
                 hyps = fit_batch(Xn, np.stack([pb["y"] for _, pb in members], 1), pb0["kind"], pb0["ls_prior"],
-                                 pb0["noise_prior"], standardize=pb0["standardize"])
+                                 pb0["noise_prior"], standardize=pb0["standardize"],
+                                 outputscale_prior=pb0["os_prior"], scaled=pb0["scaled"])
                 for (s, pb), h in zip(members, hyps):
                     s._set_state(pb["Xt"], pb["y"], pb["lo"], pb["hi"], pb["kind"], h)
             if not rest:

@@ -224,6 +224,45 @@ int evr_mll_plan_create_members(void* stream, int kind, int B, int n, int d, con
  * 1 / n scaling. */
 int evr_mll_assemble_members(int B, const int* nvalid, int d, const double* prior, const double* x,
                              const double* terms, const double* gls, double* ll, double* g);
+/* ---- scaled kernel: k = sigma^2 k_base (gpytorch ScaleKernel around RBF / Matérn) ------------
+ * The MLL gradient pieces of the lengthscales and of the outputscale sigma^2 in one pass over W:
+ *   out = [gls (B x d) | gos (B)],
+ *   gls[b][k] = sigma^2_b sum_ij W[b][i][j] dk_base[i][j] / d ls[b][k]   (dK/dls = sigma^2 dk_base/dls)
+ *   gos[b]    = sum_ij W[b][i][j] k_base[i][j]                           (dK/dsigma^2 = k_base)
+ * evr_kernel_lengthscale_grad's dispatch, lane order and row partials, one column wider; k_base and
+ * its derivative factor come from one exponential per pair.  outputscale: B doubles.
+ * work: B*n*(d+1) doubles (per-row partials, summed in a fixed order: no atomics, bitwise
+ * reproducible). */
+int evr_kernel_hyper_grad(void* stream, int kind, int B, int n, int d, const double* X, const double* lengthscales,
+                          const double* outputscale, const double* W, double* out, double* work);
+/* Member form.  Unlike the lengthscale pieces, gos is not blind to the identity padding (a padded
+ * row has W_ii = -1 and k_base(0) = 1), so the sums run over the member's own rows and columns
+ * i, j < nvalid[b] only (nvalid: B ints, device): every piece is the member's own GP's. */
+int evr_kernel_hyper_grad_members(void* stream, int kind, int B, int n, int d, const double* Xb, const int* nvalid,
+                                  const double* lengthscales, const double* outputscale, const double* W, double* out,
+                                  double* work);
+/* evr_kernel_matrix_members with K = outputscale[b] k_base + diag_add[b] I on the member's real
+ * block; the padding stays the identity. */
+int evr_kernel_matrix_members_scaled(void* stream, int kind, int B, int n, int d, const double* Xb, const int* nvalid,
+                                     const double* lengthscales, const double* outputscale, const double* diag_add,
+                                     double* K);
+/* MLL plans of the scaled kernel.  evr_mll_plan_eval reads params = [ls (B x d) | noise (B) |
+ * constant (B) | outputscale (B)] and writes out = [terms (B x 5) | gls (B x d) | gos (B) |
+ * info (B)] (gls, gos as evr_kernel_hyper_grad).  evr_mll_plan_eval, evr_mll_fit_rounds and
+ * evr_mll_plan_destroy take either kind of plan; for a scaled plan evr_mll_fit_rounds' member
+ * dimension is d + 3, x = [noise, constant, raw lengthscales, raw outputscale] (softplus), params
+ * is B x (d + 3), and prior has nine entries: ls, noise, outputscale x (family, a, b). */
+int evr_mll_plan_create_scaled(void* stream, int kind, int B, int n, int d, const double* Xn, const double* Y,
+                               evr_mll_plan** out);
+int evr_mll_plan_create_scaled_members(void* stream, int kind, int B, int n, int d, const double* Xb, const double* Y,
+                                       const int* nvalid, evr_mll_plan** out);
+/* Host-only.  evr_mll_assemble[_members] for the scaled kernel: x is B x (d + 3), g likewise, prior
+ * has nine entries; the outputscale prior is evaluated on sigma^2 = softplus(raw) and
+ * g[d + 2] = (gos / 2 + d log prior / d sigma^2) sigmoid(raw) / n. */
+int evr_mll_assemble_scaled(int B, int n, int d, const double* prior, const double* x, const double* terms,
+                            const double* gls, const double* gos, double* ll, double* g);
+int evr_mll_assemble_scaled_members(int B, const int* nvalid, int d, const double* prior, const double* x,
+                                    const double* terms, const double* gls, const double* gos, double* ll, double* g);
 /* One member's L-BFGS-B after its evaluation at x (f, g): scipy's driver loop up to the next
  * evaluation request or the end (the state machine evr_mll_fit_rounds applies). */
 int evr_lbfgsb_advance(void* run, double f, const double* g, double* x, int* task, int* nit, int* nfev,
